@@ -17,7 +17,15 @@ starts N fresh rank processes of this script (RANK / LOCAL_RANK / WORLD_SIZE /
 MASTER_ADDR=127.0.0.1 / MASTER_PORT in their environment), forwards rank 0's JSON
 line and exits non-zero if any rank failed.
 
-Prints ONE JSON line (rank 0).  `roofline` prices the step kernel alone against HBM:
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the K steps and prints the headline
+(`value` env-steps/s, `ms_per_step`, the workload's `config`; with N > 1 also how many done gathers ran in
+the timed region).  `--dump-outputs DIR` writes what the last timed step handed its caller (see
+dump_outputs) before the line is printed.  Everything that takes runs of its own -- the step-kernel
+event timing and the `roofline` built on it, the per-rank device info, the episode / line totals, the
+stand-alone gather timing, the extra roofline runs (4 Mi envs, 10x40, copy peak) and `cpu_baseline` --
+is measured only with `--full`.
+
+With --full, `roofline` prices the step kernel alone against HBM:
 algorithmic bytes per env-step = the board planes actually stored, read + written
 (2 * n_planes * word: 8 planes at 10x20 / 10x40) + the 47 B of SURVEY 8(d)'s fixed
 part = 111 B at 10x20, 175 B at 10x40 (SURVEY's own 127 / 207 B priced ten unpacked
@@ -41,6 +49,8 @@ sys.path.insert(0, ROOT)
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md: 8.0 TB/s spec, ~6.3 TB/s measured float4 copy)
 FIXED_BYTES = 47       # action 4 + piece r/w 2 + bag r/w 2 + obs 32 + reward 4 + done/lines/n_valid 3
 FIXED_BYTES_NO_OBS = 15
+DUMP_BUDGET_BYTES = 60 * 1000 * 1000  # --dump-outputs writes at most this much (a seeded sample of envs beyond it)
+DUMP_SAMPLE_SEED = 0
 
 
 def algorithmic_bytes_per_env_step(n_planes, word_bytes, with_obs=True):
@@ -81,6 +91,31 @@ def load_traffic(columns, rows, pieces, envs, lib_hash=None):
     except Exception:
         pass
     return None
+
+
+def dump_outputs(out_dir, envs, suffix=""):
+    """What the last timed step returned to its caller -- obs [B, 8] (unless --no-obs), reward, done, lines
+    [B] and the action [B] the kernel drew for each env -- over this rank's shards in env order, as float32
+    `out_dir/<name><suffix>.npy`.  When the arrays of all envs would pass DUMP_BUDGET_BYTES, the same seeded,
+    sorted sample of env rows is written for every array."""
+    import numpy as np
+    import torch
+
+    def cat(name):
+        parts = [getattr(e, name) for e in envs]
+        return parts[0] if len(parts) == 1 else torch.cat(parts)
+
+    names = (["obs"] if envs[0].compute_obs else []) + ["reward", "done", "lines", "action"]
+    arrays = {n: cat(n).cpu().numpy().astype(np.float32) for n in names}
+    n_envs = len(arrays["reward"])
+    row_bytes = sum(a.nbytes for a in arrays.values()) // n_envs
+    rows = None
+    if row_bytes * n_envs > DUMP_BUDGET_BYTES:
+        rng = np.random.default_rng(DUMP_SAMPLE_SEED)
+        rows = np.sort(rng.choice(n_envs, DUMP_BUDGET_BYTES // row_bytes, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    for n, a in arrays.items():
+        np.save(os.path.join(out_dir, n + suffix + ".npy"), a if rows is None else a[rows])
 
 
 def cpu_baseline(C, R, pieces, seconds=12.0):
@@ -130,9 +165,16 @@ def parse_args(argv=None):
     ap.add_argument("--columns", type=int, default=10)
     ap.add_argument("--pieces", default="default")
     ap.add_argument("--gather-every", type=int, default=64)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure what takes runs of its own: step-kernel event time + "
+                         "roofline, per-rank device info, episode totals, gather time, the extra roofline runs and "
+                         "the CPU baseline (a plain run prints the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32; with N > 1 ranks "
+                         "every rank writes DIR/<name>.rank<r>.npy)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the extra roofline keys (4 Mi-env run, 10x40 run, copy peak)")
+                    help="with --full: skip the extra roofline keys (4 Mi-env run, 10x40 run, copy peak)")
     ap.add_argument("--no-obs", action="store_true", help="skip the observation output (32 B per env-step less)")
     ap.add_argument("--fuse", type=int, default=1,
                     help="env-steps per kernel launch (tetris_hip_step_many: boards stay in registers between the "
@@ -145,7 +187,7 @@ def parse_args(argv=None):
                     help="capture this many steps in one HIP graph (VecTetris.capture_steps) and replay it: still "
                          "one kernel launch per step on the device, one graph launch per G steps on the host; for "
                          "small batches where the host enqueue is as long as the kernel (not combined with --fuse)")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0)
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="with --full: CPU baseline time budget")
     return ap.parse_args(argv)
 
 
@@ -412,6 +454,50 @@ def run_rank(args, device=None):
         tt = torch.tensor([dt], dtype=torch.float64, device=dev if backend == "nccl" else "cpu")
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, envs, "" if world == 1 else ".rank%d" % rank)
+
+    def headline():
+        return {
+            "metric": "env-steps/sec",
+            "value": B * world * args.steps / dt,
+            "unit": "env-steps/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": dt / args.steps * 1e3,
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": "u32" if env.desc.word_bytes == 4 else "u64",
+            "data": "synthetic",
+            "config": {"workload": "%d envs/GPU x %d GPU, %dx%d board, pieces=%s, uniform random valid actions, "
+                                   "in-kernel auto-reset, device bag seed 0" % (B, world, args.columns, args.rows,
+                                                                                args.pieces),
+                       "envs_per_gpu": B, "observation_output": not args.no_obs,
+                       "env_steps_per_launch": 1 if graph_steps > 1 else fuse, "steps_per_graph_replay": graph_steps,
+                       "streams_per_gpu": S, "board": "%dx%d" % (args.columns, args.rows), "pieces": args.pieces,
+                       "backend": backend if dist_on else "single", "device": dev.type,
+                       "sharding": "env-index ranges, no data-path collective; RCCL gathers the done counters every "
+                                   "%d steps and the done bitmask once, midway through the timed region, both on "
+                                   "a side stream" % args.gather_every},
+        }
+
+    def gathers_in_timed_region():
+        return {"counter_gathers_in_timed_region": n_gathers[0], "bitmask_gathers_in_timed_region": n_bit_gathers[0],
+                "payload": "step kernel epilogue" if payloads is not None else "pack kernel + column sum"}
+
+    if not args.full:
+        if rank == 0:
+            out = headline()
+            if dist_on:
+                out["done_gather"] = gathers_in_timed_region()
+            print(json.dumps(out), flush=True)
+        if dist_on:
+            dist.destroy_process_group()
+        return 0
+
+    # ---- --full: everything below takes runs of its own -------------------------------------------
     totals = gather.gather_counters(all_totals()).cpu().tolist()
 
     # what the collective layer itself saw: its world size and, per rank, the env range it stepped and the
@@ -536,38 +622,11 @@ def run_rank(args, device=None):
             roof["peak_copy_measured"] = extras["peak_copy_measured"]
             roof["peak_copy_how"] = "torch copy_ of 1 GiB (read + written bytes / time), same run, same device"
             roof["frac_of_copy_peak"] = achieved / extras["peak_copy_measured"]
-        out = {
-            "metric": "env-steps/sec",
-            "value": B * world * args.steps / dt,
-            "unit": "env-steps/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": dt / args.steps * 1e3,
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "u32" if wb == 4 else "u64",
-            "data": "synthetic",
-            "config": {"workload": "%d envs/GPU x %d GPU, %dx%d board, pieces=%s, uniform random valid actions, "
-                                   "in-kernel auto-reset, device bag seed 0" % (B, world, args.columns, args.rows,
-                                                                                args.pieces),
-                       "envs_per_gpu": B, "observation_output": not args.no_obs,
-                       "env_steps_per_launch": 1 if graph_steps > 1 else fuse, "steps_per_graph_replay": graph_steps,
-                       "streams_per_gpu": S, "board": "%dx%d" % (args.columns, args.rows), "pieces": args.pieces,
-                       "backend": backend if dist_on else "single", "device": dev.type,
-                       "sharding": "env-index ranges, no data-path collective; RCCL gathers the done counters every "
-                                   "%d steps and the done bitmask once, midway through the timed region, both on "
-                                   "a side stream" % args.gather_every},
-            "roofline": roof,
-            "ranks": ranks_info,
-            "episodes": totals[1], "lines_cleared": totals[2],
-        }
+        out = headline()
+        out.update(roofline=roof, ranks=ranks_info, episodes=totals[1], lines_cleared=totals[2])
         if dist_on:
-            out["done_gather"] = {"ms_per_gather": gather_ms, "counter_gathers_in_timed_region": n_gathers[0],
-                                  "bitmask_gathers_in_timed_region": n_bit_gathers[0],
-                                  "payload": "step kernel epilogue" if payloads is not None else "pack kernel + column sum",
-                                  "note": "cpu_baseline and the extra roofline keys are emitted only at world == 1"}
+            out["done_gather"] = dict(ms_per_gather=gather_ms, **gathers_in_timed_region(),
+                                      note="cpu_baseline and the extra roofline keys are emitted only at world == 1")
         if "tall_10x40" in extras:
             out["tall_10x40"] = extras["tall_10x40"]
         if world == 1 and not args.no_cpu_baseline:
@@ -590,6 +649,8 @@ def main(device=None, entry=None, prebuild=True):
     args = parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         return launch_ranks(args, entry=entry, prebuild=prebuild)
     return run_rank(args, device=device)

@@ -25,7 +25,7 @@ def _run(args, extra_env=None, timeout=280):
 
 @pytest.mark.timeout(300)
 def test_gpus_2_starts_two_ranks(host_backend):
-    r = _run(["--gpus", "2", "--steps", "8", "--warmup", "4", "--batch", "512", "--gather-every", "4"])
+    r = _run(["--gpus", "2", "--steps", "8", "--warmup", "4", "--batch", "512", "--gather-every", "4", "--full"])
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout
@@ -67,7 +67,7 @@ def test_parent_deadline(host_backend):
 
 @pytest.mark.timeout(300)
 def test_single_rank_line_and_mismatch(host_backend):
-    r = _run(["--gpus", "1", "--steps", "4", "--warmup", "2", "--batch", "256", "--no-cpu-baseline"])
+    r = _run(["--gpus", "1", "--steps", "4", "--warmup", "2", "--batch", "256", "--full", "--no-cpu-baseline"])
     assert r.returncode == 0, r.stderr[-2000:]
     out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
     assert out["n_gpus"] == 1 and "done_gather" not in out and out["config"]["device"] == "cpu"
@@ -116,3 +116,92 @@ def test_stale_traffic_profile_is_not_quoted(tmp_path, monkeypatch):
     # what counts is the hash compiled into the LOADED library
     assert bench.load_traffic(10, 20, "default", 1 << 20, lib_hash=prof["csrc_hash"]) == 123.0
     assert bench.load_traffic(10, 20, "default", 1 << 20, lib_hash="0123456789abcdef") is None
+
+
+HEADLINE_KEYS = ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step")
+FULL_ONLY_KEYS = ("roofline", "ranks", "episodes", "lines_cleared", "cpu_baseline", "tall_10x40")
+
+
+def _line(r):
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    return json.loads(lines[0])
+
+
+def _dumped(d, suffix=""):
+    import numpy as np
+    return {n: np.load(os.path.join(d, n + suffix + ".npy")) for n in ("obs", "reward", "done", "lines", "action")}
+
+
+@pytest.mark.timeout(300)
+def test_plain_run_is_lean_and_dumps_the_last_step(tmp_path, host_backend):
+    """A plain run prints the headline only; --dump-outputs holds what the last of warmup + steps returned,
+    the same from run to run, and --steps sets the number of timed steps."""
+    import numpy as np
+    import torch
+    from tetris_amd import VecTetris
+    d1, d2 = str(tmp_path / "a"), str(tmp_path / "b")
+    args = ["--gpus", "1", "--steps", "6", "--warmup", "3", "--batch", "256"]
+    out = _line(_run(args + ["--dump-outputs", d1]))
+    assert all(k in out for k in HEADLINE_KEYS) and not [k for k in FULL_ONLY_KEYS if k in out]
+    assert out["metric"] == "env-steps/sec" and out["unit"] == "env-steps/s" and out["higher_is_better"] is True
+    assert out["dtype"] == "u32" and out["steps"] == 6 and out["warmup"] == 3 and "done_gather" not in out
+    assert abs(out["value"] - 256 * 6 / (out["ms_per_step"] * 6e-3)) < 1e-6 * out["value"]
+    a = _dumped(d1)
+    assert a["obs"].shape == (256, 8) and all(a[n].shape == (256,) for n in ("reward", "done", "lines", "action"))
+    assert all(x.dtype == np.float32 for x in a.values())
+    _line(_run(args + ["--dump-outputs", d2]))
+    b = _dumped(d2)
+    for n in a:
+        np.testing.assert_array_equal(a[n], b[n])
+    # the workload bench.py times, stepped here by hand: 3 + 6 steps of the in-kernel random policy
+    env = VecTetris(10, 20, 256, device="cpu", auto_reset=True, seed=0)
+    for _ in range(9):
+        obs, rew, done, lines = env.step()
+    want = dict(obs=obs, reward=rew, done=done, lines=lines, action=env.action)
+    for n, t in want.items():
+        np.testing.assert_array_equal(a[n], t.to(torch.float32).numpy())
+    # one timed step more is another state
+    _line(_run(["--gpus", "1", "--steps", "7", "--warmup", "3", "--batch", "256", "--dump-outputs", d2]))
+    env.step()
+    np.testing.assert_array_equal(_dumped(d2)["reward"], env.reward.to(torch.float32).numpy())
+
+
+@pytest.mark.timeout(300)
+def test_two_rank_dump_is_the_whole_batch(tmp_path, host_backend):
+    """--gpus 2 plain: the gathers of the timed region are reported, nothing of --full; each rank dumps its
+    shard, and the two shards are the single-process run of both ranks' envs."""
+    import numpy as np
+    d2, d1 = str(tmp_path / "two"), str(tmp_path / "one")
+    out = _line(_run(["--gpus", "2", "--steps", "8", "--warmup", "4", "--batch", "256", "--gather-every", "4",
+                      "--dump-outputs", d2]))
+    assert out["n_gpus"] == 2 and not [k for k in FULL_ONLY_KEYS if k in out]
+    assert out["done_gather"]["counter_gathers_in_timed_region"] == 2
+    assert out["done_gather"]["bitmask_gathers_in_timed_region"] == 1 and "ms_per_gather" not in out["done_gather"]
+    # (the ranks step once more before the timed region, so that every collective is set up before it)
+    _line(_run(["--gpus", "1", "--steps", "8", "--warmup", "5", "--batch", "512", "--dump-outputs", d1]))
+    r0, r1, whole = _dumped(d2, ".rank0"), _dumped(d2, ".rank1"), _dumped(d1)
+    for n in whole:
+        np.testing.assert_array_equal(np.concatenate([r0[n], r1[n]]), whole[n])
+
+
+def test_dump_of_a_large_batch_is_a_fixed_sample(tmp_path, monkeypatch, host_backend):
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    from tetris_amd import VecTetris
+    env = VecTetris(10, 20, 1000, device="cpu", auto_reset=True, seed=0)
+    for _ in range(5):
+        env.step()
+    row_bytes = 4 * (8 + 4)
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 100 * row_bytes)
+    bench.dump_outputs(str(tmp_path / "a"), [env])
+    bench.dump_outputs(str(tmp_path / "b"), [env])
+    a, b = _dumped(str(tmp_path / "a")), _dumped(str(tmp_path / "b"))
+    assert a["obs"].shape == (100, 8) and a["reward"].shape == (100,)
+    assert sum(x.nbytes for x in a.values()) <= bench.DUMP_BUDGET_BYTES
+    for n in a:
+        np.testing.assert_array_equal(a[n], b[n])
+    rows = np.sort(np.random.default_rng(bench.DUMP_SAMPLE_SEED).choice(1000, 100, replace=False))
+    np.testing.assert_array_equal(a["obs"], env.obs.numpy()[rows])

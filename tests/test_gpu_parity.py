@@ -221,7 +221,7 @@ def test_bench_rccl_path_one_rank():
                MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5",
-                        "--no-extras", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=600)
+                        "--full", "--no-extras", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
     assert out["config"]["backend"] == "nccl" and out["config"]["device"] == "cuda"

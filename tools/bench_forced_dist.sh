@@ -3,7 +3,7 @@
 #   bash tools/bench_forced_dist.sh <out_dir> [steps] [warmup]
 OUT=${1:-gpurun_out/dist}; K=${2:-20}; W=${3:-5}
 mkdir -p $OUT
-X="--no-cpu-baseline --no-extras --steps $K --warmup $W"
+X="--full --no-cpu-baseline --no-extras --steps $K --warmup $W"
 for rep in 1 2 3; do
   timeout -k 10 200 python3 bench.py $X > $OUT/single_k${K}_$rep.json 2>/dev/null || exit 1
   TETRIS_BENCH_FORCE_DIST=1 RANK=0 LOCAL_RANK=0 WORLD_SIZE=1 MASTER_ADDR=127.0.0.1 MASTER_PORT=$((29500 + rep)) \

@@ -11,7 +11,7 @@ cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 J() { grep '^{' ; }   # (RCCL / driver banners may precede the JSON line)
 
 # 1. bench lines (N = 1): config 5 shape, 7-piece set, without obs, fused, two streams
-X="--no-cpu-baseline --no-extras"
+X="--full --no-cpu-baseline --no-extras"
 timeout -k 10 200 python3 bench.py $X --rows 40 2>/dev/null | J > $OUT/bench_n1_10x40.json || exit 1
 timeout -k 10 200 python3 bench.py $X --pieces standard7 2>/dev/null | J > $OUT/bench_n1_10x20_standard7.json || exit 1
 timeout -k 10 200 python3 bench.py $X --no-obs 2>/dev/null | J > $OUT/bench_n1_10x20_no_obs.json || exit 1
@@ -21,7 +21,7 @@ timeout -k 10 200 python3 bench.py $X --streams 2 --rows 40 2>/dev/null | J > $O
 echo "bench done"
 
 # 2. kernel trace of the same bench command (per-kernel average duration)
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 bench.py --no-cpu-baseline --no-extras --steps 300 --warmup 50 > $OUT/trace.log 2>&1 || exit 1
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 bench.py --full --no-cpu-baseline --no-extras --steps 300 --warmup 50 > $OUT/trace.log 2>&1 || exit 1
 cp $(ls $OUT/trace/*/*kernel_stats.csv | head -1) $OUT/step_kernel_stats_bench_steps300.csv
 echo "trace done"
 
@@ -31,8 +31,8 @@ timeout -k 10 250 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/pmc_wri
 python3 tools/parse_pmc.py $OUT/pmc_fetch $OUT/pmc_write > $OUT/pmc_traffic.json || exit 1
 # the headline lines last: they quote the traffic just measured (same library: source hash)
 mkdir -p profiles && cp $OUT/pmc_traffic.json profiles/pmc_traffic.json
-timeout -k 10 300 python3 bench.py 2> $OUT/bench_n1_10x20.err | J > $OUT/bench_n1_10x20.json || exit 1
-timeout -k 10 300 python3 bench.py --steps 20 --warmup 5 2>/dev/null | J > $OUT/bench_n1_10x20_driver_style_steps20.json || exit 1
+timeout -k 10 300 python3 bench.py --full 2> $OUT/bench_n1_10x20.err | J > $OUT/bench_n1_10x20.json || exit 1
+timeout -k 10 300 python3 bench.py --full --steps 20 --warmup 5 2>/dev/null | J > $OUT/bench_n1_10x20_driver_style_steps20.json || exit 1
 echo "pmc traffic + headline bench done"
 
 # 4. per-wave SQ counters of the step kernel (two passes of 8 counters)
