@@ -335,7 +335,7 @@ TET_HD int bag_draw_lut(uint32_t& bag, int n_pieces, uint32_t r16, const uint8_t
 // whole word to itself on purpose: the kernels are integer-VALU bound while the LDS pipe idles,
 // so fields are fetched ready to use (wide LDS reads) instead of being shifted out of packed words.
 struct alignas(16) OrientEntry {  // 48 bytes = three 16-byte LDS reads (field order matters for that)
-  uint32_t sh[4];      // per footprint column j: 10 * (need_j - 1) + j, a shift into the level word
+  uint32_t sh[4];      // per footprint column j: 16 * (4 - need_j) + j, a shift into the level word
   uint32_t rj0[2];     // rescue rows t = 1, 2 (board rows R-3+t): first piece column of that row,
   uint32_t rj1[2];     //   last piece column; rj0 = 31 when the piece has no such row
   uint32_t vert4;      // all ones for the vertical Straight, else 0
@@ -690,13 +690,12 @@ TET_HD void bcts_features(const W (&col)[C], const int (&h)[C], int R, const uin
 //      terminal  <=>  e := a + H - R  >  n_cleared.
 // All columns c of one orientation are evaluated at once on C-bit column sets:
 //  * slack s_c = R - h_c; footprint column j needs s_{c+j} >= need_j = H - b_j.
-//    B_l = {c : s_c < l} for l = 1..4 (built with byte-parallel compares of the packed
-//    heights) sit in 10-bit fields of one 64-bit level word Z = [0 | B_1 | B_2 | B_3 | B_4];
-//    Z >> (10 (need_j - 1) + j) has B_{need_j - 1} >> j in bits 0-9 and B_{need_j} >> j in bits
-//    10-19, so ONE shift per footprint column yields both "pokes >= 1 row above R-1" (I1, OR
-//    over j of bits 10-19) and "pokes >= 2 rows" (I2, bits 0-9; level 0 is the empty field).
-//    Bits of c + j >= 10 spill over from the next field: those placements do not exist and are
-//    removed by fullmask.
+//    B_l = {c : s_c < l} for l = 1..4 sit in 16-bit fields of one 64-bit level word, level l in field
+//    4 - l: Z = [B_4 | B_3 | B_2 | B_1 | (0)] from bit 0 upwards;
+//    Z >> (16 (4 - need_j) + j) has B_{need_j} >> j in bits 0-15 and B_{need_j - 1} >> j in bits
+//    16-31, so ONE shift per footprint column yields both "pokes >= 1 row above R-1" (I1, OR
+//    over j of bits 0-15) and "pokes >= 2 rows" (I2, bits 16-31; level 0 is what lies beyond bit 63).
+//    Placements with c + j >= C do not exist and are removed by fullmask.
 //  * e = 1 (I1 & ~I2): the anchor is exactly a = R+1-H, so the piece's row rho sits
 //    in board row R-3+t, t = rho+4-H.  That row becomes full iff all its missing
 //    columns lie inside the piece's (contiguous) run [c+j0, c+j1] of that row, i.e.
@@ -706,64 +705,114 @@ TET_HD void bcts_features(const W (&col)[C], const int (&h)[C], int R, const uin
 //    be full (no stack cell sits at row >= R), so t <= 2.
 //  * e >= 2 can only be rescued when H = 4 (vertical Straight): rows R-2 and R-1 must
 //    both miss exactly column c (X_t & Y_t is that single column, or empty).
-// stride of the level fields of valid_mask's level word: 10 bits up to ten columns (the paper's boards: the
-// shifts below then stay in the range the round-1/2 kernels were tuned on), 12 bits for 11 and 12 columns
-TET_HD constexpr int level_stride(int C) { return C <= 10 ? 10 : 12; }
+// Layout of the level word Z: 16-bit fields, level l in field 4 - l, Z = [B_4 | B_3 | B_2 | B_1 | (0)]
+// from bit 0 upwards, i.e. two 32-bit words lo = B_4 | B_3 << 16, hi = B_2 | B_1 << 16 that are put together
+// without any 64-bit arithmetic.  Z >> (16 (4 - need_j) + j) then has B_{need_j} >> j in bits 0-15 (I1) and
+// B_{need_j - 1} >> j in bits 16-31 (I2; for need_j = 1 that is what lies beyond bit 63: zeros, the empty
+// level 0).  A field holds C <= 12 bits, so what a shift by j <= 3 pulls in from the next field lands at
+// bits >= 13 and is cut by the column mask.
+// TOP (env_step sets it on 32-bit boards of up to ten columns): the board holds no cell at or above row R
+// (it is what a valid placement leaves), so h_c > R - l <=> column c has a cell in rows
+// R-l .. R-1 and the level sets are the suffix-ORs of the top four rows, transposed.  w_c = col[c] >> (R - 4)
+// is those four cells of one column; the columns c, c+4, c+8 are packed at their own distance (bit 4e + r =
+// row R-4+r of column c + 4e) and ONE multiply by (1 + 2^15) << c lays rows 0 / 1 of all three at bits
+// c + 4e / 16 + c + 4e (and, two bits further up, rows 2 / 3): ~30 vector instructions for the 4 x C
+// transpose against ~80 for the byte-parallel height compares, and the rows themselves are what the
+// rescue needs (the general form gathers them a second time, three bits per column).
+constexpr int kLevelStride = 16;
 template <int C> struct MissBits { typedef uint32_t type; };   // 3 bits per column: 32 bits up to 10 columns,
 template <> struct MissBits<11> { typedef uint64_t type; };    // 64 beyond
 template <> struct MissBits<12> { typedef uint64_t type; };
 TET_HD int ctz_any(uint32_t x) { return __builtin_ctz(x); }
 TET_HD int ctz_any(uint64_t x) { return __builtin_ctzll(x); }
 
-template <typename W, int C>
+template <typename W, int C, bool TOP = false>
 TET_HD uint64_t valid_mask(const W (&col)[C], const int (&h)[C], const OrientEntry* tab, uint64_t fullmask, int R) {
-  static_assert(C <= 12, "four 12-bit level fields + one empty field fill the 64-bit level word; 12-bit mask fields");
-  constexpr int LS = level_stride(C);
+  static_assert(C <= 12, "16-bit level fields; 12-bit mask fields");
+  static_assert(!TOP || (sizeof(W) == 4 && C <= 10), "the top-rows form is written for 32-bit boards of up to ten columns");
+  constexpr int LS = kLevelStride;
   typedef typename MissBits<C>::type FT;
-  uint32_t P[3] = {0u, 0u, 0u};
+  const uint32_t cm = (1u << C) - 1u;
+  uint32_t zlo, zhi;   // the level word
+  uint32_t b3;         // level set 3 (for the rescue test)
+  uint32_t mrow[3] = {0u, 0u, 0u};  // TOP: missing cells of rows R-3, R-2, R-1, bit c = column c
+  if constexpr (TOP) {
+    uint32_t lo = 0, hi = 0;
 #pragma unroll
-  for (int c = 0; c < C; ++c) P[c >> 2] |= (uint32_t)h[c] << (8 * (c & 3));
-  uint32_t lv[4];
+    for (int g = 0; g < 4 && g < C; ++g) {
+      uint32_t pk = (uint32_t)(col[g] >> (R - 4));
+      uint32_t sel = 1u;
+      if (g + 4 < C) { pk |= (uint32_t)(col[g + 4] >> (R - 4)) << 4; sel |= 1u << 4; }
+      if (g + 8 < C) { pk |= (uint32_t)(col[g + 8] >> (R - 4)) << 8; sel |= 1u << 8; }
+      const uint32_t u = pk * (0x8001u << g);          // pk << g  |  pk << (15 + g): disjoint, no carries
+      const uint32_t mk = (sel * 0x10001u) << g;
+      lo |= u & mk;                                    // rows R-4 | R-3 << 16
+      hi |= (u >> 2) & mk;                             // rows R-2 | R-1 << 16
+    }
+    zhi = hi | (hi >> 16);                             // B_2 | B_1 << 16
+    zlo = lo | (lo >> 16) | ((zhi & 0xFFFFu) * 0x10001u);  // B_4 | B_3 << 16
+    b3 = zlo >> 16;
+    mrow[0] = ~(lo >> 16) & cm;
+    mrow[1] = ~hi & cm;
+    mrow[2] = ~(hi >> 16) & cm;
+  } else {
+    uint32_t P[3] = {0u, 0u, 0u};
 #pragma unroll
-  for (int l = 1; l <= 4; ++l) {
-    // byte b of P + K has bit 7 set iff h_b > R - l  (h <= 63, K <= 127: no carry between bytes)
-    const uint32_t K = (uint32_t)(127 - (R - l)) * 0x01010101u;
-    uint32_t g = 0;
+    for (int c = 0; c < C; ++c) P[c >> 2] |= (uint32_t)h[c] << (8 * (c & 3));
+    uint32_t lv[4];
 #pragma unroll
-    for (int q = 0; q < (C + 3) / 4; ++q)
-      g |= ((((P[q] + K) & 0x80808080u) * 0x00204081u) >> 28) << (4 * q);  // gather the four bit-7s
-    lv[l - 1] = g;
+    for (int l = 1; l <= 4; ++l) {
+      // byte b of P + K has bit 7 set iff h_b > R - l  (h <= 63, K <= 127: no carry between bytes)
+      const uint32_t K = (uint32_t)(127 - (R - l)) * 0x01010101u;
+      uint32_t g = 0;
+#pragma unroll
+      for (int q = 0; q < (C + 3) / 4; ++q)
+        g |= ((((P[q] + K) & 0x80808080u) * 0x00204081u) >> 28) << (4 * q);  // gather the four bit-7s
+      lv[l - 1] = g;
+    }
+    zlo = lv[3] | (lv[2] << LS);
+    zhi = lv[1] | (lv[0] << LS);
+    b3 = lv[2];
   }
-  const uint64_t Z = ((uint64_t)lv[0] << LS) | ((uint64_t)lv[1] << (2 * LS)) | ((uint64_t)lv[2] << (3 * LS)) |
-                     ((uint64_t)lv[3] << (4 * LS));
+  const uint64_t Z = ((uint64_t)zhi << 32) | zlo;
   // A placement that pokes above row R - 1 is rescued only by a row among R-3 .. R-1 that the piece
   // completes, i.e. one that misses at most four cells.  A cell in row R-3 or above means h >= R - 2
   // (level set 3), so when fewer than C - 4 columns reach that height no such row exists: the whole
   // rescue evaluation (a third of this function) is skipped -- by the wavefront, when none of its
   // envs needs it, which is the rule for boards that are not stacked to the top.
-  const bool rescue = !TET_RESCUE_SKIP || TET_WAVE_ANY(popc(lv[2]) >= C - 4);
+  const bool rescue = !TET_RESCUE_SKIP || TET_WAVE_ANY(popc(b3) >= C - 4);
   uint32_t X[3] = {0u, 0u, 0u}, Y[3] = {0u, 0u, 0u};
   uint32_t rv1 = 0, rv2 = 0;
   if (rescue) {
-    FT Fall = 0;
+    if constexpr (TOP) {
 #pragma unroll
-    for (int c = 0; c < C; ++c) Fall |= (FT)((uint32_t)(col[c] >> (R - 3)) & 7u) << (3 * c);  // cells of rows R-3..R-1
-    const FT Mall = (FT)~Fall;  // missing cells, 3 bits per column
-    constexpr FT kEveryThird = (FT)0x9249249249249249ull & (FT)(((FT)1 << (3 * C)) - 1);  // bit 3c
-    constexpr FT kTop = (FT)1 << (8 * sizeof(FT) - 1);
+      for (int t = 0; t < 3; ++t) {
+        const uint32_t m = mrow[t];                                      // bit c: column c misses row R-3+t
+        const int lo = __builtin_ctz(m | 0x80000000u);
+        const int hi = bitlen((uint32_t)(m | 1u)) - 1;
+        X[t] = ~0u << hi;
+        Y[t] = m ? (2u << lo) - 1u : 0u;  // a full row (only on boards that were set from outside) rescues nothing
+      }
+    } else {
+      FT Fall = 0;
 #pragma unroll
-    for (int t = 0; t < 3; ++t) {
-      const FT m = (FT)(Mall >> t) & kEveryThird;                     // bit 3c: column c misses row R-3+t
-      const int lo = (ctz_any((FT)(m | kTop)) * 11) >> 5;              // / 3
-      const int hi = ((bitlen((FT)(m | 1)) - 1) * 11) >> 5;            // (bitlen: the top bit of m is never set)
-      X[t] = ~0u << hi;
-      Y[t] = m ? (2u << lo) - 1u : 0u;  // a full row (only on boards that were set from outside) rescues nothing
+      for (int c = 0; c < C; ++c) Fall |= (FT)((uint32_t)(col[c] >> (R - 3)) & 7u) << (3 * c);  // cells of rows R-3..R-1
+      const FT Mall = (FT)~Fall;  // missing cells, 3 bits per column
+      constexpr FT kEveryThird = (FT)0x9249249249249249ull & (FT)(((FT)1 << (3 * C)) - 1);  // bit 3c
+      constexpr FT kTop = (FT)1 << (8 * sizeof(FT) - 1);
+#pragma unroll
+      for (int t = 0; t < 3; ++t) {
+        const FT m = (FT)(Mall >> t) & kEveryThird;                     // bit 3c: column c misses row R-3+t
+        const int lo = (ctz_any((FT)(m | kTop)) * 11) >> 5;              // / 3
+        const int hi = ((bitlen((FT)(m | 1)) - 1) * 11) >> 5;            // (bitlen: the top bit of m is never set)
+        X[t] = ~0u << hi;
+        Y[t] = m ? (2u << lo) - 1u : 0u;  // a full row (only on boards that were set from outside) rescues nothing
+      }
     }
     const uint32_t s0 = X[0] & Y[0], s1 = X[1] & Y[1], s2 = X[2] & Y[2];
     rv1 = s0 | s1 | s2;  // vertical Straight: any of its three lower rows
     rv2 = s1 & s2;       //                    / both of R-2, R-1
   }
-  const uint32_t cm = (1u << C) - 1u;
   uint64_t mask = 0;
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
@@ -771,7 +820,7 @@ TET_HD uint64_t valid_mask(const W (&col)[C], const int (&h)[C], const OrientEnt
     uint32_t r = 0;
 #pragma unroll
     for (int j = 0; j < 4; ++j) r |= (uint32_t)(Z >> e.sh[j]);
-    const uint32_t i1 = r >> LS, i2 = r;
+    const uint32_t i1 = r, i2 = r >> LS;
     uint32_t v = ~i1;
     if (rescue) {
       // rescue by one cleared row (e = 1)
@@ -1165,7 +1214,7 @@ TET_HD void env_step(W (&col)[C], uint64_t& meta, int action, bool use_policy, c
   const uint8_t* sel_nib = hole_lut + (PACKW ? AfterLut::kSelNib : LutLayout<CR>::kSelNib);
   int np = draw >= 0 ? draw : bag_draw_lut(bag, cfg.n_pieces, rnd >> 16, sel_nib);
   uint64_t nmask = (TET_ABLATE & 2) ? (tab.fullmask[np] ^ (uint64_t)h[0])
-                                    : valid_mask<W, C>(col, h, piece_entries(tab, np), tab.fullmask[np], R);
+                                    : valid_mask<W, C, (sizeof(W) == 4 && C <= 10)>(col, h, piece_entries(tab, np), tab.fullmask[np], R);
   int nnv = popc(nmask);
   int done = nnv == 0;
   out.reward = k - 1 + (done ? -100 : 0);  // game.py:86,89-90 (rewards :34-35)

@@ -56,15 +56,15 @@ inline int n_placements(int pid, int C) {
 }
 
 // thresholds: footprint column j needs slack R - h >= need_j = H - b_j.  valid_mask keeps the
-// column sets B_l = {c : slack < l} in LS-bit fields of one 64-bit word (level l at bit LS l, LS =
-// tet::level_stride(C): 10 up to ten columns, else 12); the shift LS (need_j - 1) + j lines column c + j
-// of level need_j up with bit LS + c and of level need_j - 1 with bit c.
-inline void pack_mask_fields(const CatOrient& o, OrientEntry* e, int C) {
-  const int LS = level_stride(C);
+// column sets B_l = {c : slack < l} in 16-bit fields of one 64-bit word (level l in field 4 - l,
+// tet::kLevelStride); the shift 16 (4 - need_j) + j lines column c + j of level need_j up with bit c
+// and of level need_j - 1 with bit 16 + c (need_j = 1: beyond bit 63, the empty level 0).
+inline void pack_mask_fields(const CatOrient& o, OrientEntry* e) {
+  const int LS = kLevelStride;
   int H = 0;
   for (int j = 0; j < o.w; ++j)
     if (o.b[j] + o.n[j] > H) H = o.b[j] + o.n[j];
-  for (int j = 0; j < o.w; ++j) e->sh[j] = (uint32_t)(LS * (H - o.b[j] - 1) + j);
+  for (int j = 0; j < o.w; ++j) e->sh[j] = (uint32_t)(LS * (4 - (H - o.b[j])) + j);
   for (int j = o.w; j < 4; ++j) e->sh[j] = e->sh[0];  // absent columns repeat column 0's term (OR is idempotent)
   e->vert4 = (o.w == 1 && H == 4) ? ~0u : 0u;
   for (int t = 1; t < 3; ++t) {  // board row R-3+t holds piece row rho when the anchor is R+1-H
@@ -93,7 +93,7 @@ inline void build_table(const TetrisDesc* d, SetTable* t) {
       for (int oi = 0; oi < p.n_orient[l]; ++oi) {
         OrientEntry* e = &t->orient[i][l * 2 + oi];
         e->desc = pack_orient(p.o[l][oi]);
-        pack_mask_fields(p.o[l][oi], e, C);
+        pack_mask_fields(p.o[l][oi], e);
         for (int c = 0; c + p.o[l][oi].w <= C; ++c) full |= 1ull << mask_bit(2 * l + oi, c);
       }
     t->fullmask[i] = full;
