@@ -246,6 +246,19 @@ TET_HD int bitlen(uint64_t x) { return 63 - __builtin_clzll((x << 1) | 1ull); }
 template <typename W>
 TET_HD W lowmask(int n) { return (W)(((W)1 << n) - 1); }
 
+// acc + sum over the four bytes of |a.byte - b.byte|   (one v_sad_u8 on the device)
+TET_HD uint32_t sad_u8(uint32_t a, uint32_t b, uint32_t acc) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __builtin_amdgcn_sad_u8(a, b, acc);
+#else
+  for (int k = 0; k < 4; ++k) {
+    const int d = (int)((a >> (8 * k)) & 255u) - (int)((b >> (8 * k)) & 255u);
+    acc += (uint32_t)(d < 0 ? -d : d);
+  }
+  return acc;
+#endif
+}
+
 // ---- counter-based bag (build design; same distribution as popping a fresh
 // np.random.permutation front to back, tetromino.py:17-22) ------------------
 TET_HD uint32_t mix32(uint32_t x) {
@@ -339,8 +352,10 @@ struct alignas(16) OrientEntry {  // 48 bytes = three 16-byte LDS reads (field o
   uint32_t rj0[2];     // rescue rows t = 1, 2 (board rows R-3+t): first piece column of that row,
   uint32_t rj1[2];     //   last piece column; rj0 = 31 when the piece has no such row
   uint32_t vert4;      // all ones for the vertical Straight, else 0
+  uint32_t set_w4;     // the same in every entry of a table: nonzero iff some piece of the SET has a four-column
+                       //   orientation (else sh[3] repeats sh[0] everywhere and valid_mask drops that term)
   uint32_t desc;       // packed Orient descriptor (above)
-  uint32_t pad_[2];
+  uint32_t pad_;
 };
 static_assert(sizeof(OrientEntry) == 48, "table staging and LDS reads assume 48-byte entries");
 
@@ -358,7 +373,7 @@ TET_HD const OrientEntry* piece_entries(const SetTable& tab, int np) {
   return reinterpret_cast<const OrientEntry*>(reinterpret_cast<const char*>(&tab.orient[0][0]) + off);
 }
 
-// feature tables (tools/gen_feature_lut.py), staged in LDS by the kernels as ONE block of byte
+// feature tables (tools/gen_feature_lut.py), staged in LDS by the kernels as ONE block.  Byte
 // tables, one per field so nothing has to be shifted or masked out of a packed entry:
 // hole_A, hole_u (index: a CR-row chunk of a column + the cell above), wells_S, wells_lead,
 // wells_trail (index: a CR-row chunk of a column's well cells).  CR = 12 rows per chunk in general
@@ -372,16 +387,26 @@ struct LutLayout {
   // select tables (the same in every set): k-th placement of a 4-column group of one loop's two
   // orientation fields in the reference's order; k-th set bit of a nibble
   static constexpr int kSelPair = kWellsTrail + kWellsEntries, kSelNib = kSelPair + 256 * 8;
-  static constexpr int kBytes = kSelNib + 16 * 4;
+  static constexpr int kByteTablesEnd = kSelNib + 16 * 4;  // what every form but board_features_u32_2x10 reads
+  // CR = 10 only: packed entries behind the select tables, for board_features_u32_2x10 (32-bit boards of up to ten
+  // columns), which reads [kSelPair, kBytes) and none of the byte tables.  hole_pack: uint16 u | A << 8 per hole
+  // index; wells_pack: uint32 trail | lead << 8 | S << 16 per wells index.  One read where the byte tables take
+  // two / three, and the entries are added as whole words and split once per board.
+  static constexpr int kPackHole = kByteTablesEnd, kPackWells = kPackHole + 2 * kHoleEntries;
+  static constexpr int kBytes = CR == 10 ? kPackWells + 4 * kWellsEntries : kByteTablesEnd;
 };
+// which kernels run board_features_u32_2x10 (and stage only the part of the tables it reads)
+template <typename W, int C, int NCH, int CR, bool PACKW = false>
+TET_HD constexpr bool features_packed() { return sizeof(W) == 4 && C <= 10 && NCH == 2 && CR == 10 && !PACKW; }
 constexpr int kFeatureLutBytes = LutLayout<12>::kBytes;
 constexpr int kFeatureLut10Bytes = LutLayout<10>::kBytes;
 // tables of the afterstate kernels (tetris_after_lut.inc): the hole tables for 12-row chunks at the
 // offsets of LutLayout<12>, then ONE 32-bit entry per 12-row chunk of a column's well cells,
 // S | trail << 16 | lead << 24.  The afterstate walk re-evaluates the wells of up to five columns per
 // placement and is bound by the number of LDS reads (one pipe per CU, 3-4-way bank conflicts on
-// random indices), so it fetches the three fields with one read; the stepping kernels are bound by
-// vector instructions and keep the ready-to-use byte tables.
+// random indices), so it fetches the three fields with one read.  The step kernel's headline form does the
+// same with the packed entries of LutLayout<10> (board_features_u32_2x10: the LDS pipe, shared by the four
+// SIMDs of a CU, was the busier unit there too); the other stepping forms keep the byte tables.
 struct AfterLut {
   static constexpr int kHoleA = LutLayout<12>::kHoleA, kHoleU = LutLayout<12>::kHoleU;
   static constexpr int kWellsPack = 2 * LutLayout<12>::kHoleEntries;
@@ -619,12 +644,105 @@ TET_HD int col_wells_packed(W x, W L, W Rr, int hi, int R, bool left_wall, bool 
   return (int)total;
 }
 
-// state.py:175-280.  out = f0,f1,f2,f4,f5,f7.
+// board_features on the headline path of the stepping kernels: 32-bit boards of up to ten columns, two
+// 10-row chunks.  Same sums as the general form below, term by term, with the per-column work that is
+// not a table read taken out of the loop:
+//  * no integer heights.  n_c = clz(x_c << 1 | 1) = 31 - h_c is all a column needs: lowmask(h_c) =
+//    0x7FFFFFFF >> n_c, "empty" is x_c == 0, and height DIFFERENCES are the differences of the n_c;
+//  * the row-transition terms max(hL - h, 0).  The signed differences hL - h telescope from the wall
+//    height R down to h_{C-1}, so  sum max(hL - h, 0) = (sum |hL - h| + R - h_{C-1}) / 2.  The n_c are
+//    packed four to a word (P) beside the same bytes moved up one column with the wall's 31 - R in front
+//    (Q); three byte-wise sums of absolute differences give sum |hL - h|, and the first unused byte of P
+//    (zero) meets n_{C-1} in Q, which adds exactly the R - h_{C-1} = n_{C-1} - (31 - R) that is wanted
+//    once the wall's constant is taken off.  (C a multiple of four has no such byte: added by hand.);
+//  * one table read per chunk instead of two (holes) / two or three (wells): packed entries
+//    (LutLayout<10>::kPackHole, kPackWells) are added as whole words and split once per board; only the
+//    products across the chunk border take a byte out of an entry.  40 fewer LDS reads per board.  The reads
+//    are what the kernel waits for: the LDS pipe serves all four SIMDs of a CU.
+template <int C>
+TET_HD void board_features_u32_2x10(const uint32_t (&col)[C], int R, const uint8_t* lut, int& rows_with_holes,
+                                    int& col_trans, int& holes, int& wells, int& row_trans, int& hole_depth) {
+  static_assert(C <= 12, "three words of packed heights");
+  typedef LutLayout<10> LL;
+  constexpr int CR = 10;
+  const uint16_t* hole_pack = reinterpret_cast<const uint16_t*>(lut + LL::kPackHole);
+  const uint32_t* wells_pack = reinterpret_cast<const uint32_t*>(lut + LL::kPackWells);
+  const uint32_t wall = lowmask<uint32_t>(R + 4);
+  const uint32_t nwall = (uint32_t)(31 - R);
+  uint32_t n[C];
+  uint32_t P[3] = {0u, 0u, 0u};
+#pragma unroll
+  for (int c = 0; c < C; ++c) {
+    n[c] = (uint32_t)__builtin_clz((col[c] << 1) | 1u);
+    P[c >> 2] |= n[c] << (8 * (c & 3));
+  }
+  uint32_t sad = (C % 4 == 0) ? n[C - 1] : 0u;
+#pragma unroll
+  for (int q = 0; q < (C + 3) / 4; ++q) {
+    const uint32_t Q = (P[q] << 8) | (q == 0 ? nwall : (P[q > 0 ? q - 1 : 0] >> 24));
+    sad = sad_u8(P[q], Q, sad);
+  }
+  uint32_t hole_rows = 0;
+  uint32_t hsum = 0, wsum = 0;  // sums of whole table entries: u | A << 8,  trail | lead << 8 | S << 16
+  uint32_t f2 = 0, f4 = 0, f7 = 0;  // f4, f7: the products across the chunk border
+  uint32_t f5 = (uint32_t)(R - popc(col[C - 1])) + ((sad - nwall) >> 1);  // state.py:190 + the height steps
+  uint32_t f5neg = 0;                                                      // empty columns: see col_rowtrans
+  uint32_t nh_left = 0;
+#pragma unroll
+  for (int i = 0; i < C; ++i) {
+    const uint32_t x = col[i];
+    const uint32_t L = (i == 0) ? wall : col[i > 0 ? i - 1 : 0];
+    const uint32_t Rr = (i == C - 1) ? wall : col[i + 1 < C ? i + 1 : i];
+    const uint32_t lm = 0x7FFFFFFFu >> n[i];               // lowmask(h)
+    const uint32_t ho = ~x & lm;                           // holes (state.py:210-213)
+    const uint32_t nh = (uint32_t)popc(ho);
+    f2 += nh;
+    hole_rows |= ho;                                       // state.py:215
+    f5 += (uint32_t)popc((x ^ L) & lm);
+    f5neg += (x == 0u) ? nh_left : 0u;
+    nh_left = nh;
+    if (!(TET_ABLATE & 16)) {                              // col_own, chunks 0 and 1
+      const uint32_t i0 = x & (uint32_t)(LL::kHoleEntries - 1), i1 = x >> CR;
+      const uint32_t e0 = hole_pack[i0];
+      hsum += e0 + hole_pack[i1];
+      f7 += (e0 & 255u) * (uint32_t)popc(i1);              // run tops of chunk 0 x the cells above the chunk
+    }
+    if (!(TET_ABLATE & 32)) {                              // col_wells, chunks 0 and 1
+      uint32_t w = ~x & L & Rr;
+      if (i == 0 || i == C - 1) w &= 0x7FFFFFFFu >> (n[i] < nwall ? n[i] : nwall);  // lowmask(max(h, R))
+      const uint32_t i0 = w & (uint32_t)(LL::kWellsEntries - 1), i1 = w >> CR;
+      const uint32_t e0 = wells_pack[i0], e1 = wells_pack[i1];
+      wsum += e0 + e1;
+      f4 += (e0 & 255u) * ((e1 >> 8) & 255u);              // a run across the chunk border: trail x lead
+    }
+    if (TET_FENCE_EVERY > 0 && i % TET_FENCE_EVERY == TET_FENCE_EVERY - 1 && i + 1 < C) {
+      TET_PIN(hsum);
+      TET_PIN(wsum);
+      TET_PIN(f2);
+      TET_PIN(f4);
+      TET_PIN(f5);
+      TET_PIN(f7);
+      TET_SCHED_FENCE();
+    }
+  }
+  rows_with_holes = popc(hole_rows);  // state.py:274-275
+  col_trans = C + 2 * (int)(hsum & 255u);  // one unconditional transition per column (state.py:194) + two per run top
+  holes = (int)f2;
+  wells = (int)(f4 + (wsum >> 16));
+  row_trans = (int)(f5 - f5neg);
+  hole_depth = (int)(f7 + (hsum >> 8));
+}
+
+// state.py:175-280.  out = f0,f1,f2,f4,f5,f7.  h = heights_of(col).
 // PACKW: hole_lut is an AfterLut (packed wells entries) instead of a LutLayout<CR>
 template <typename W, int C, int NCH = 0, int CR = 12, bool PACKW = false>
 TET_HD void board_features(const W (&col)[C], const int (&h)[C], int R, const uint8_t* hole_lut,
                            int& rows_with_holes, int& col_trans, int& holes, int& wells, int& row_trans,
                            int& hole_depth) {
+  if constexpr (features_packed<W, C, NCH, CR, PACKW>()) {
+    board_features_u32_2x10<C>(col, R, hole_lut, rows_with_holes, col_trans, holes, wells, row_trans, hole_depth);
+    return;
+  }
   const W wall = lowmask<W>(R + 4);  // walls of ones over every stored row (state.py:177-178)
   W hole_rows = 0;
   int f1 = C;                      // one unconditional transition per column (state.py:194)
@@ -720,6 +838,7 @@ TET_HD void bcts_features(const W (&col)[C], const int (&h)[C], int R, const uin
 // transpose against ~80 for the byte-parallel height compares, and the rows themselves are what the
 // rescue needs (the general form gathers them a second time, three bits per column).
 constexpr int kLevelStride = 16;
+template <int N> struct IntConst { static constexpr int value = N; };
 template <int C> struct MissBits { typedef uint32_t type; };   // 3 bits per column: 32 bits up to 10 columns,
 template <> struct MissBits<11> { typedef uint64_t type; };    // 64 beyond
 template <> struct MissBits<12> { typedef uint64_t type; };
@@ -813,24 +932,34 @@ TET_HD uint64_t valid_mask(const W (&col)[C], const int (&h)[C], const OrientEnt
     rv1 = s0 | s1 | s2;  // vertical Straight: any of its three lower rows
     rv2 = s1 & s2;       //                    / both of R-2, R-1
   }
+  // No piece of the set is four columns wide (wave-uniform: one table word, the same in every entry): sh[3]
+  // repeats sh[0] everywhere and the fourth shift and OR of each orientation are dropped.  Two copies of
+  // the loop, not a test inside it: the entry's shifts stay one wide LDS read.
   uint64_t mask = 0;
+  auto orientations = [&](auto nj) {
+    constexpr int NJ = decltype(nj)::value;
 #pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const OrientEntry& e = tab[k];
-    uint32_t r = 0;
+    for (int k = 0; k < 4; ++k) {
+      const OrientEntry& e = tab[k];
+      uint32_t r = 0;
 #pragma unroll
-    for (int j = 0; j < 4; ++j) r |= (uint32_t)(Z >> e.sh[j]);
-    const uint32_t i1 = r, i2 = r >> LS;
-    uint32_t v = ~i1;
-    if (rescue) {
-      // rescue by one cleared row (e = 1)
-      uint32_t r1 = ((X[1] >> e.rj1[0]) & (Y[1] >> e.rj0[0])) | ((X[2] >> e.rj1[1]) & (Y[2] >> e.rj0[1]));
-      r1 = (rv1 & e.vert4) | (r1 & ~e.vert4);
-      const uint32_t r2 = rv2 & e.vert4;
-      v |= ~(i2 & ~r2) & r1;
+      for (int j = 0; j < NJ; ++j) r |= (uint32_t)(Z >> e.sh[j]);
+      const uint32_t i1 = r, i2 = r >> LS;
+      uint32_t v = ~i1;
+      if (rescue) {
+        // rescue by one cleared row (e = 1)
+        uint32_t r1 = ((X[1] >> e.rj1[0]) & (Y[1] >> e.rj0[0])) | ((X[2] >> e.rj1[1]) & (Y[2] >> e.rj0[1]));
+        r1 = (rv1 & e.vert4) | (r1 & ~e.vert4);
+        const uint32_t r2 = rv2 & e.vert4;
+        v |= ~(i2 & ~r2) & r1;
+      }
+      mask |= (uint64_t)(v & cm) << (kFieldStride * k);
     }
-    mask |= (uint64_t)(v & cm) << (kFieldStride * k);
-  }
+  };
+  if (TET_WAVE_ANY(tab[0].set_w4 != 0u))
+    orientations(IntConst<4>());
+  else
+    orientations(IntConst<3>());
   return mask & fullmask;
 }
 

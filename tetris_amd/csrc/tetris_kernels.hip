@@ -104,15 +104,29 @@ __device__ __forceinline__ void stage_after_lut(uint8_t* lds) {
 template <typename W, int C, int BLK, int CR, bool AFTER = false>
 struct alignas(16) StepLds {
   SetTable tab;
-  alignas(16) uint8_t lut[AFTER ? tet::kAfterLutBytes : tet::LutLayout<CR>::kBytes];  // AFTER: a tet::AfterLut
+  // AFTER: a tet::AfterLut; else the tables at their own offsets, up to the last byte this geometry's kernels read
+  // (NCH = 2 is the only chunk count 32-bit boards run with the 10-row tables)
+  alignas(16) uint8_t lut[AFTER ? tet::kAfterLutBytes
+                                : (tet::features_packed<W, C, 2, CR>() ? tet::LutLayout<CR>::kBytes : tet::LutLayout<CR>::kByteTablesEnd)];
   W lane_cols[C][BLK];  // per-lane scratch for the runtime-indexed stamp (bank = lane)
 };
 
-template <int CR = 12>
+// The part of the feature tables a stepping kernel reads, in 16-byte units [begin, end): the byte tables and
+// the select tables, or -- where tet::board_features_u32_2x10 runs -- the select tables and the packed entries
+// behind them.  LDS holds the whole block at its own offsets either way; the rest is never touched.
+template <typename W, int C, int NCH, int CR>
+constexpr int lut_stage_begin() { return tet::features_packed<W, C, NCH, CR>() ? tet::LutLayout<CR>::kSelPair / 16 : 0; }
+template <typename W, int C, int NCH, int CR>
+constexpr int lut_stage_end() {
+  return (tet::features_packed<W, C, NCH, CR>() ? tet::LutLayout<CR>::kBytes : tet::LutLayout<CR>::kByteTablesEnd) / 16;
+}
+static_assert(tet::LutLayout<10>::kSelPair % 16 == 0 && tet::LutLayout<10>::kByteTablesEnd % 16 == 0 && tet::LutLayout<10>::kBytes % 16 == 0, "staged as uint4");
+
+template <typename W, int C, int NCH, int CR>
 __device__ __forceinline__ void stage_hole_lut(uint8_t* lds) {
   const uint4* src = feature_lut_src<CR>();
   uint4* dst = reinterpret_cast<uint4*>(lds);
-  for (int t = threadIdx.x; t < tet::LutLayout<CR>::kBytes / 16; t += blockDim.x) dst[t] = src[t];
+  for (int t = lut_stage_begin<W, C, NCH, CR>() + (int)threadIdx.x; t < lut_stage_end<W, C, NCH, CR>(); t += blockDim.x) dst[t] = src[t];
 }
 
 __device__ __forceinline__ void stage_table(SetTable& lds, const SetTable& arg) {
@@ -259,8 +273,9 @@ __global__ __launch_bounds__(BLK, (step_waves<W, CR>())) void step_kernel(const 
   StepInputs<W, C> in;
   load_inputs<W, C, PACK>(p, i, in);
   {
-    constexpr int kLutVecs = tet::LutLayout<CR>::kBytes / 16, kLutPerLane = (kLutVecs + kBlock - 1) / kBlock;
-    const uint4* lsrc = feature_lut_src<CR>();
+    constexpr int kLutVec0 = lut_stage_begin<W, C, NCH, CR>();
+    constexpr int kLutVecs = lut_stage_end<W, C, NCH, CR>() - kLutVec0, kLutPerLane = (kLutVecs + kBlock - 1) / kBlock;
+    const uint4* lsrc = feature_lut_src<CR>() + kLutVec0;
     uint4 lv[kLutPerLane];
 #pragma unroll
     for (int q = 0; q < kLutPerLane; ++q) {  // (clamped, not predicated: keeps lv[] in registers)
@@ -276,7 +291,7 @@ __global__ __launch_bounds__(BLK, (step_waves<W, CR>())) void step_kernel(const 
 #pragma unroll
     for (int q = 0; q < kLutPerLane; ++q)
       if (!(TET_ABLATE & 128) && (kLutVecs % kBlock == 0 || (int)threadIdx.x + q * kBlock < kLutVecs))
-        reinterpret_cast<uint4*>(hole_lut)[threadIdx.x + q * kBlock] = lv[q];
+        reinterpret_cast<uint4*>(hole_lut)[kLutVec0 + threadIdx.x + q * kBlock] = lv[q];
 #pragma unroll
     for (int q = 0; q < kTabPerLane; ++q)
       if ((int)threadIdx.x + q * kBlock < kTabWords) reinterpret_cast<uint32_t*>(&tab)[threadIdx.x + q * kBlock] = tw[q];
@@ -411,7 +426,7 @@ __global__ __launch_bounds__(step_block<W>(), (POLICY == 0 ? step_waves<W, CR>()
   StepInputs<W, C> in;
   load_inputs<W, C, PACK>(p, i, in);
   if (AFTER) stage_after_lut(hole_lut);
-  else stage_hole_lut<CR>(hole_lut);
+  else stage_hole_lut<W, C, NCH, CR>(hole_lut);
   stage_table(tab, p.tab);
   unsigned n_inv = 0, n_done = 0, n_lines = 0, n_steps = 0;
   StepCfg cfg = p.cfg;

@@ -98,6 +98,15 @@ inline void build_table(const TetrisDesc* d, SetTable* t) {
       }
     t->fullmask[i] = full;
   }
+  // set-wide: some orientation is four columns wide (valid_mask reads it from the first entry of any piece)
+  uint32_t w4 = 0;
+  for (int i = 0; i < d->n_pieces; ++i) {
+    const CatPiece& p = kCatalogue[d->piece_ids[i]];
+    for (int l = 0; l < 2; ++l)
+      for (int oi = 0; oi < p.n_orient[l]; ++oi) w4 |= p.o[l][oi].w >= 4 ? 1u : 0u;
+  }
+  for (int i = 0; i < kMaxPieces; ++i)
+    for (int k = 0; k < 4; ++k) t->orient[i][k].set_w4 = w4;
 }
 
 // num_columns values the kernels are instantiated for (one place for the

@@ -25,6 +25,13 @@ tetris_core.hpp):
       k-th set bit in that order (0 where k is past the last one).
   sel_nib [16 * 4]     index nib * 4 + k: position of the k-th set bit of a nibble (bag draw).
 
+tetris_feature_lut10.inc only, after sel_nib (the step kernels' form for 32-bit boards of up to ten columns,
+tet::board_features_u32_2x10, which stages sel_pair .. the end and not the byte tables):
+  hole_pack [2048 * 2]   (little-endian uint16 entries) index as hole_A / hole_u:  u | A << 8.  Entries are
+      ADDED as whole words (sum of u over a board <= 100 stays inside its byte) and split once per board.
+  wells_pack [1024 * 4]  (little-endian uint32 entries) index as wells_S:  trail | lead << 8 | S << 16.  Added as
+      whole words too (the sums of trail and of lead over two chunks of ten columns are <= 200 each, S on top).
+
 tetris_after_lut.inc (tet::AfterLut, the afterstate kernels): hole_A [8192], hole_u [8192] as above for
 12-row chunks, then sel_pair / sel_nib as above after
   wells_pack [4096 * 4]  (little-endian uint32 entries) index v = a 12-row chunk of a column's well-cell
@@ -66,7 +73,13 @@ def tables(cr):
         wells_s.append(S)
         wells_lead.append(lead)
         wells_trail.append(trail)
-    return hole_a + hole_u + wells_s + wells_lead + wells_trail + select_tables()
+    out = hole_a + hole_u + wells_s + wells_lead + wells_trail + select_tables()
+    if cr == 10:  # packed entries for tet::board_features_u32_2x10
+        for v in range(1 << (cr + 1)):
+            out += [hole_u[v], hole_a[v]]
+        for v in range(1 << cr):
+            out += [wells_trail[v], wells_lead[v], wells_s[v], 0]
+    return out
 
 
 def select_tables():
@@ -109,7 +122,7 @@ print("tetris_after_lut.inc", len(vals))
 
 for cr, name in ((12, "tetris_feature_lut.inc"), (10, "tetris_feature_lut10.inc")):
     vals = tables(cr)
-    assert len(vals) == 2 * (1 << (cr + 1)) + 3 * (1 << cr) + 2048 + 64 and len(vals) % 16 == 0
+    assert len(vals) == 2 * (1 << (cr + 1)) + 3 * (1 << cr) + 2048 + 64 + (8 * (1 << cr) if cr == 10 else 0) and len(vals) % 16 == 0
     out = os.path.join(CSRC, name)
     with open(out, "w") as f:
         f.write("// generated by tools/gen_feature_lut.py (%d-row chunks) -- do not edit\n" % cr)
