@@ -9,6 +9,8 @@ import numpy as np
 import pytest
 import torch
 
+import directed_boards as db
+
 STANDARD7 = ["Straight", "RCorner", "LCorner", "Square", "SnakeR", "SnakeL", "T"]
 
 
@@ -244,31 +246,7 @@ def mask_rescue_stress(device, orc, n_boards=1500, R=20, C=10, seed=0):
     :36).  Valid masks / n_valid / feature rows vs the oracle for all nine pieces."""
     from tetris_amd import VecTetris
     from tetris_amd.tetromino import CATALOGUE
-    rng = np.random.default_rng(seed)
-    rows = R + 4
-    cells = np.zeros((n_boards, rows, C), np.int8)
-    for b in range(n_boards):
-        hts = rng.integers(R - 5, R + 1, size=C)
-        for c in range(C):
-            hc = int(hts[c])
-            colv = (rng.random(hc) > 0.15).astype(np.int8)
-            if hc:
-                colv[hc - 1] = 1
-            cells[b, :hc, c] = colv
-        # make 1-3 of the top rows nearly full: missing run of width 1..4
-        for r in rng.choice(np.arange(R - 4, R), size=rng.integers(1, 4), replace=False):
-            w = int(rng.integers(1, 5))
-            c0 = int(rng.integers(0, C - w + 1))
-            cells[b, r, :] = 1
-            cells[b, r, c0:c0 + w] = 0
-            # columns in the gap must not have cells above the gap row (heights stay consistent)
-            cells[b, r:, c0:c0 + w] = 0
-        for r in range(rows):  # no full rows in a reachable board
-            if cells[b, r].sum() == C:
-                cells[b, r, rng.integers(0, C)] = 0
-        # cells above a removed cell may now float: that is fine for the reference semantics
-        # as long as heights are recomputed from the board (State(lowest_free_rows=None))
-        cells[b, R:, :] = 0
+    cells = db.near_top(n_boards, R, C, seed)
     desc = orc.make_desc(C, R, list(CATALOGUE))
     env = VecTetris(C, R, n_boards, device=device, pieces=list(CATALOGUE))
     n_rescued = 0
@@ -958,3 +936,280 @@ def done_bit_packing(device):
         want = (dd.view(-1, 8) * w).sum(dim=1).to(torch.uint8)
         assert torch.equal(got, want), n
         assert torch.equal(unpack_done_bits(got, n), d)
+
+
+# ---- directed boards through the step kernels ------------------------------------------------------
+
+# Directed boards (tests/directed_boards.py) through the step kernels, by kernel variant:
+DIRECTED_GEOMETRIES = [
+    (5, 20), (6, 20), (7, 20), (8, 20), (9, 20), (10, 20),  # packed u32 boards, packed feature entries, top-rows mask
+    (10, 10), (10, 13), (6, 4), (10, 4),                    # chunk borders inside / at the top of the board
+    (11, 20), (12, 20),                                     # u32, byte-table features
+    (10, 24), (11, 27),                                     # u32, one plane per column (NCH = 0), 12-row chunks
+    (10, 40), (9, 40), (12, 40),                            # u64 (9x40: the kernel of the last-VGPR hazard)
+    (10, 32), (10, 33), (10, 44), (10, 45),                 # u64 chunk-count switches
+    (12, 59),                                               # tallest, widest
+]
+STEP_MANY_GEOMETRIES = [(10, 20), (7, 20), (12, 20), (10, 24), (10, 40), (9, 40)]
+
+
+class DirectedCases:
+    """Case list of one geometry: env i = (board bix[i], current piece pcs[i], first action act[i]), built from the
+    oracle alone (orc.placements), so that the same list drives the kernels and the oracle."""
+
+    def __init__(self, orc, C, R, n_near_top, seed=7):
+        from tetris_amd.tetromino import CATALOGUE
+        self.C, self.R, self.n_near_top = C, R, n_near_top
+        self.catalogue = list(CATALOGUE)
+        self.boards = np.concatenate([db.near_top(n_near_top, R, C, seed), db.structured(R, C, seed)])
+        self.names = ["near_top #%d" % b for b in range(n_near_top)] + db.structured_names(R, C)
+        assert len(self.names) == len(self.boards)
+        db.check_boards(self.boards, R)
+        desc = orc.make_desc(C, R, self.catalogue)
+        n_valid = np.zeros((len(self.catalogue), len(self.boards)), np.int64)
+        self.n_rescued = 0
+        for pi, name in enumerate(self.catalogue):
+            for b in range(len(self.boards)):
+                out = orc.placements(desc, self.boards[b], name)
+                term = out["terminal"].astype(bool)
+                n_valid[pi, b] = int((~term).sum())
+                if b < n_near_top:  # counted as mask_rescue_stress counts them
+                    self.n_rescued += int(((out["anchor_row"] + 0 >= 0) & (~term) & (out["n_cleared"] > 0) &
+                                           (out["heights"].max(axis=1) + out["n_cleared"] > R)).sum())
+        self.n_valid_table = n_valid
+        self.bix, self.pcs, self.act = db.expand(self.boards, n_valid)
+        self.n_cases = len(self.bix)
+
+    def padded(self, pad_to):
+        """(bix, pcs, act) repeated cyclically to pad_to envs."""
+        if pad_to is None:
+            return self.bix, self.pcs, self.act
+        assert pad_to >= self.n_cases
+        ix = np.arange(pad_to) % self.n_cases
+        return self.bix[ix], self.pcs[ix], self.act[ix]
+
+
+_DIRECTED = {}
+
+
+def directed_cases(orc, C, R, n_near_top=60):
+    key = (C, R, n_near_top)
+    if key not in _DIRECTED:
+        _DIRECTED[key] = DirectedCases(orc, C, R, n_near_top)
+    return _DIRECTED[key]
+
+
+class _Where:
+    """Names the env of a mismatch: geometry, env index, board family, piece, action(s)."""
+
+    def __init__(self, cs, tag, bix, pcs, act):
+        self.cs, self.tag, self.bix, self.pcs, self.act = cs, tag, bix, pcs, act
+        self.act2 = None
+
+    def env(self, i):
+        s = "env %d: board %d (%s), piece %s, action %d" % (
+            i, self.bix[i], self.cs.names[self.bix[i]], self.cs.catalogue[self.pcs[i]], self.act[i])
+        if self.act2 is not None:
+            s += ", then action %d" % self.act2[i]
+        return s
+
+    def eq(self, got, want, what, sel=None):
+        """Bit-exact comparison of a per-env output (on the envs `sel` if given)."""
+        got = got.cpu().numpy() if isinstance(got, torch.Tensor) else np.asarray(got)
+        want = want.cpu().numpy() if isinstance(want, torch.Tensor) else np.asarray(want)
+        if got.dtype == np.bool_ or want.dtype == np.bool_:
+            got, want = got.astype(np.bool_), want.astype(np.bool_)
+        assert got.shape == want.shape, (self.tag, what, got.shape, want.shape)
+        bad = (got != want).reshape(len(got), -1).any(axis=1)
+        if sel is not None:
+            bad &= sel
+        if bad.any():
+            i = int(np.nonzero(bad)[0][0])
+            raise AssertionError("%dx%d %s: %s differs on %d of %d envs; first %s:\n got  %s\n want %s" % (
+                self.cs.C, self.cs.R, self.tag, what, int(bad.sum()), len(got), self.env(i),
+                np.array2string(got[i], threshold=2000, max_line_width=200),
+                np.array2string(want[i], threshold=2000, max_line_width=200)))
+
+
+def _directed_stream(B, L):
+    """Replay stream [L, B]: row 0 is taken by the constructor's reset; rows 1 and 2 make every catalogue piece the
+    next piece on every kind of board; the further rows (drawn by an auto-reset) shift that pattern."""
+    i = np.arange(B)
+    stream = np.zeros((L, B), np.uint8)
+    stream[1] = i % 9
+    stream[2] = (i // 9) % 9
+    for r in range(3, L):
+        stream[r] = (i // 9 + i + r) % 9
+    return stream
+
+
+def _refresh_leaves_state(env, w, when):
+    """The step kernel's next-piece valid mask (top-rows form) == the general form of the refresh kernel: all 64 bits
+    of meta and n_valid survive a refresh."""
+    meta, nv = env.meta.clone(), env.n_valid.clone()
+    env.refresh()
+    w.eq(env.meta, meta, "meta (valid mask) after refresh, %s" % when)
+    w.eq(env.n_valid, nv, "n_valid after refresh, %s" % when)
+
+
+def _second_actions(n_valid):
+    nv = n_valid.astype(np.int64)
+    i = np.arange(len(nv), dtype=np.int64)
+    return np.where(nv > 0, (i * 2654435761 >> 7) % np.maximum(nv, 1), 0).astype(np.int32)
+
+
+def _compare_step(env, ref, w, when, sel=None):
+    w.eq(env.obs, ref.obs, "obs, " + when, sel)
+    w.eq(env.reward, ref.reward, "reward, " + when, sel)
+    w.eq(env.done, ref.done, "done, " + when, sel)
+    w.eq(env.lines, ref.lines, "lines, " + when, sel)
+    w.eq(env.n_valid, ref.n_valid, "n_valid, " + when, sel)
+    w.eq(env.piece, ref.piece, "piece, " + when, sel)
+    w.eq(env.boards(), ref.cells, "boards, " + when)
+
+
+def _two_steps(device, orc, cs, bix, pcs, act, auto_reset):
+    """set_boards, step 1 (env i plays act[i]), step 2 (a hashed valid action) on a replay-stream env in lock-step with
+    the oracle, the refresh check after each; returns (env, ref, step-1 outputs of the oracle)."""
+    from tetris_amd import VecTetris
+    C, R, B = cs.C, cs.R, len(bix)
+    w = _Where(cs, "auto_reset=%s B=%d" % (auto_reset, B), bix, pcs, act)
+    stream = _directed_stream(B, 6 if auto_reset else 4)
+    cells = cs.boards[bix]
+    env = VecTetris(C, R, B, device=device, pieces=cs.catalogue, auto_reset=auto_reset, piece_stream=stream)
+    ref = orc.OracleVecEnv(C, R, B, pieces=cs.catalogue, auto_reset=auto_reset, piece_stream=stream, nthreads=0)
+    env.set_boards(cells, pcs)
+    ref.cells[:] = cells
+    ref.piece[:] = pcs
+    # 1. the refresh kernel's count against the oracle's placements
+    w.eq(env.n_valid, cs.n_valid_table[pcs, bix], "n_valid after set_boards")
+    # 2. step 1: every case plays its own action
+    env.step(torch.from_numpy(act))
+    _, _, _, _, n_bad = ref.step(act)
+    assert n_bad == 0, (C, R, n_bad)
+    _compare_step(env, ref, w, "step 1")
+    env.check()
+    first = dict(obs=ref.obs.copy(), lines=ref.lines.copy(), done=ref.done.copy(), n_valid=ref.n_valid.copy(),
+                 piece=ref.piece.copy())
+    state1 = dict(cols=env.cols.clone(), meta=env.meta.clone(), reward=env.reward.clone(), done=env.done.clone(),
+                  lines=env.lines.clone())
+    # 3. top-rows valid mask == general form
+    _refresh_leaves_state(env, w, "step 1")
+    # 4. step 2: a wrong mask bit with the right popcount becomes a wrong placement
+    act2 = _second_actions(ref.n_valid)
+    w.act2 = act2
+    env.step(torch.from_numpy(act2))
+    ref.step(act2)
+    live = ref.invalid == 0
+    assert live.any()
+    if auto_reset:
+        assert live.all()  # finished envs were reset: every env has a valid action
+    _compare_step(env, ref, w, "step 2", sel=live)
+    _refresh_leaves_state(env, w, "step 2")
+    return w, first, state1, live
+
+
+def step_directed_boards(device, orc, C, R, n_near_top=60, pad_to=None):
+    """tetris_hip_step against the oracle from hand-built boards (directed_boards.py), every catalogue piece as the
+    current and as the next piece, one env per (board, piece, valid action): outputs of two steps bit-exact, the step
+    kernel's next-piece valid mask against the refresh kernel's, compute_obs=False and auto-reset twins.  Returns the
+    figures of the coverage conditions (asserted here from the oracle's outputs alone)."""
+    from tetris_amd import VecTetris
+    cs = directed_cases(orc, C, R, n_near_top)
+    bix, pcs, act = cs.padded(pad_to)
+    B = len(bix)
+    w, first, state1, live = _two_steps(device, orc, cs, bix, pcs, act, auto_reset=False)
+    # coverage, from the oracle alone
+    hist = np.bincount(first["lines"], minlength=5)
+    n_done, n_dead = int(first["done"].sum()), int((first["n_valid"] == 0).sum())
+    figures = dict(C=C, R=R, B=B, lines_hist=hist.tolist(), done=n_done, n_valid_next_0=n_dead, rescued=cs.n_rescued,
+                   max_obs=first["obs"].max(axis=0).tolist())
+    print("directed boards %dx%d: %s" % (C, R, figures))
+    assert len(hist) == 5 and (hist[1:] >= 5).all(), figures
+    assert n_done >= 100 and n_dead >= 1 and cs.n_rescued > 0, figures
+    assert len(np.unique(pcs)) == 9 and len(np.unique(first["piece"])) == 9, figures
+    assert not live.all()  # the finished envs of step 1 are flagged in step 2 (no auto-reset)
+    # 5. compute_obs=False twin of step 1: identical dynamics, obs untouched
+    twin = VecTetris(C, R, B, device=device, pieces=cs.catalogue, auto_reset=False, piece_stream=_directed_stream(B, 4),
+                     compute_obs=False)
+    twin.set_boards(cs.boards[bix], pcs)
+    twin.step(torch.from_numpy(act))
+    w.tag += " compute_obs=False"
+    w.act2 = None
+    for k in ("cols", "meta", "reward", "done", "lines"):
+        got, want = getattr(twin, k), state1[k]
+        if k == "cols":  # [tiles, planes, 64] -> one row per env
+            got, want = (x.permute(0, 2, 1).reshape(-1, x.shape[1])[:B] for x in (got, want))
+        w.eq(got, want, k + " of the twin without obs")
+    assert not twin.obs.any()
+    # 6. auto-reset twin: finished envs draw two pieces and restart inside the kernel
+    _two_steps(device, orc, cs, bix, pcs, act, auto_reset=True)
+    return figures
+
+
+def step_many_directed_boards(device, orc, C, R, n_near_top=60, seed=21):
+    """tetris_hip_step_many from the directed boards (device bag, auto-reset): three fused random-policy steps against
+    three tetris_hip_step launches and the oracle, then two fused greedy steps from the same boards against
+    step(greedy_actions())."""
+    from tetris_amd import VecTetris
+    cs = directed_cases(orc, C, R, n_near_top)
+    bix, pcs, act = cs.padded(None)
+    B = len(bix)
+    cells = cs.boards[bix]
+    w = _Where(cs, "step_many B=%d" % B, bix, pcs, act)
+    a = VecTetris(C, R, B, device=device, pieces=cs.catalogue, auto_reset=True, seed=seed)
+    b = VecTetris(C, R, B, device=device, pieces=cs.catalogue, auto_reset=True, seed=seed)
+    ref = orc.OracleVecEnv(C, R, B, pieces=cs.catalogue, auto_reset=True, seed=seed, nthreads=0)
+
+    def inject():
+        a.set_boards(cells, pcs)
+        b.set_boards(cells, pcs)
+        ref.cells[:] = cells
+        ref.piece[:] = pcs
+
+    def compare_state(when):
+        w.eq(a.cols.permute(0, 2, 1).reshape(-1, a.n_planes)[:B], b.cols.permute(0, 2, 1).reshape(-1, b.n_planes)[:B],
+             "cols, fused vs single steps, " + when)
+        w.eq(a.meta, b.meta, "meta, fused vs single steps, " + when)
+        w.eq(a.boards(), ref.cells, "boards, " + when)
+        w.eq(b.boards(), ref.cells, "boards of the single-step env, " + when)
+
+    inject()
+    out = a.step_many(3)
+    lines_seen = np.zeros(5, np.int64)
+    n_done = 0
+    for k in range(3):
+        b.step()
+        _, _, _, _, n_bad = ref.step()
+        assert n_bad == 0
+        when = "random policy, step %d" % (k + 1)
+        for name, single, want in (("action", b.action, ref.action), ("obs", b.obs, ref.obs),
+                                   ("reward", b.reward, ref.reward), ("done", b.done, ref.done),
+                                   ("lines", b.lines, ref.lines), ("n_valid", b.n_valid, ref.n_valid),
+                                   ("piece", b.piece, ref.piece)):
+            w.eq(out[name][k], single, "%s, fused vs single step, %s" % (name, when))
+            w.eq(out[name][k], want, "%s, %s" % (name, when))
+        lines_seen += np.bincount(ref.lines, minlength=5)
+        n_done += int(ref.done.sum())
+    compare_state("after 3 random steps")
+    assert a.stats() == b.stats() and a.stats()["invalid"] == 0
+    assert (lines_seen[1:] > 0).all() and n_done > 0, (lines_seen, n_done)  # (from the oracle alone)
+    # greedy policy, from the same boards
+    inject()
+    w.tag = "step_many greedy B=%d" % B
+    out = a.step_many(2, policy="greedy")
+    for k in range(2):
+        ba, _ = b.greedy_actions()
+        played = torch.where(ba >= 0, ba, torch.zeros_like(ba))  # -1 = no valid action: play 0, as greedy_policy does
+        b.step(played.clone())
+        ref.step(played.cpu().numpy())
+        live = ref.invalid == 0
+        assert live.any()
+        when = "greedy policy, step %d" % (k + 1)
+        w.eq(out["action"][k], played, "action, fused vs greedy_actions, " + when, live)
+        for name, single, want in (("obs", b.obs, ref.obs), ("reward", b.reward, ref.reward), ("done", b.done, ref.done),
+                                   ("lines", b.lines, ref.lines), ("n_valid", b.n_valid, ref.n_valid),
+                                   ("piece", b.piece, ref.piece)):
+            w.eq(out[name][k], single, "%s, fused vs single step, %s" % (name, when), live)
+            w.eq(out[name][k], want, "%s, %s" % (name, when), live)
+    compare_state("after 2 greedy steps")

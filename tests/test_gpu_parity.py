@@ -246,3 +246,21 @@ def test_unsupported_widths_are_refused():
 
 def test_golden_wide_trajectories(orc, golden_dir):
     pc.golden_wide_trajectories(DEV, orc, golden_dir)
+
+
+@pytest.mark.parametrize("C,R", pc.DIRECTED_GEOMETRIES)
+def test_step_directed_boards(orc, C, R):
+    """tetris_hip_step from hand-built boards (gap rows, wells, towers, checkerboard, near-top stacks), all nine
+    pieces as current and next piece, against the oracle; one geometry per kernel variant and chunk border."""
+    pc.step_directed_boards(DEV, orc, C, R)
+
+
+def test_step_directed_boards_large_tile(orc):
+    """The same cases repeated past 65,536 envs: the 512-env-tile step kernel instead of the 256-env-tile one."""
+    for C, R in ((10, 20), (7, 20), (12, 20)):
+        pc.step_directed_boards(DEV, orc, C, R, pad_to=65536 + 333)
+
+
+@pytest.mark.parametrize("C,R", pc.STEP_MANY_GEOMETRIES)
+def test_step_many_directed_boards(orc, C, R):
+    pc.step_many_directed_boards(DEV, orc, C, R)

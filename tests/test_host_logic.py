@@ -137,3 +137,17 @@ def test_rollouts_fed_pieces(host_backend, orc, golden_dir):
 
 def test_golden_wide_trajectories(host_backend, orc, golden_dir):
     pc.golden_wide_trajectories(DEV, orc, golden_dir)
+
+
+@pytest.mark.parametrize("C,R", pc.DIRECTED_GEOMETRIES)
+def test_step_directed_boards(host_backend, orc, C, R):
+    pc.step_directed_boards(DEV, orc, C, R)
+
+
+def test_step_directed_boards_large_tile(host_backend, orc):
+    pc.step_directed_boards(DEV, orc, 10, 20, pad_to=65536 + 333)
+
+
+@pytest.mark.parametrize("C,R", pc.STEP_MANY_GEOMETRIES)
+def test_step_many_directed_boards(host_backend, orc, C, R):
+    pc.step_many_directed_boards(DEV, orc, C, R)
