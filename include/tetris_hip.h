@@ -257,8 +257,10 @@ int tetris_hip_afterstates(const TetrisDesc* desc, const void* cols, const uint6
  * sum_k features[k] * weights[k] (float32, left to right) of every placement.
  *  weights     : HOST pointer to 8 floats (game.py:111-118 uses -24.04 -19.77 -13.08 -12.63
  *                -10.49 -9.22 6.6 -1.61)
- *  best_action : int32[B]  first non-terminal action of maximal fitness (-1: none)
- *  best_value  : float32[B] or NULL
+ *  best_action : int32[B]  first non-terminal action of maximal fitness (-1: none); of several
+ *                actions that reach the maximum exactly, the one with the lowest index
+ *  best_value  : float32[B] or NULL: that maximum; 0 for an env without a non-terminal action
+ *                (n_valid == 0, best_action -1)
  *  fitness_all : float32[B][a_max] or NULL: every placement in raw order, terminal
  *                included (the domain of get_best_policy, game.py:103)
  */

@@ -309,6 +309,15 @@ def step_without_obs(device, orc, B=300):
         assert torch.equal(picked, obs)
 
 
+def fit(feats, w32):
+    """Tetris.fitness (game.py:109-118 under NumPy >= 2): float32 products and sums, left to right."""
+    feats, w32 = np.asarray(feats, np.float32), np.asarray(w32, np.float32)
+    acc = feats[..., 0] * w32[0]
+    for q in range(1, 8):
+        acc = (acc + feats[..., q] * w32[q]).astype(np.float32)
+    return acc
+
+
 def greedy_policy(device, orc, golden_dir, B=400):
     """tetris_hip_policy_greedy vs (a) float32 left-to-right fitness of the oracle's features and
     (b) the get_best_policy vectors recorded from the reference (g6)."""
@@ -316,23 +325,17 @@ def greedy_policy(device, orc, golden_dir, B=400):
     from tetris_amd.tetromino import CATALOGUE
     w32 = np.array(VecTetris.BCTS_WEIGHTS, np.float32)
 
-    def fit(feats):  # game.py:109-118 under NumPy >= 2: float32 products and sums, left to right
-        acc = feats[..., 0] * w32[0]
-        for q in range(1, 8):
-            acc = (acc + feats[..., q] * w32[q]).astype(np.float32)
-        return acc
-
     env = VecTetris(10, 20, B, device=device, pieces="standard7", auto_reset=True, seed=8)
     ref = orc.OracleVecEnv(10, 20, B, pieces="standard7", auto_reset=True, seed=8)
     for t in range(40):
         ba, bv, fa = env.greedy_actions(include_fitness=True)
         rf, rnv, rfa, rna = ref.afterstates(include_terminal=True)
-        want_all = fit(rfa)
+        want_all = fit(rfa, w32)
         got = fa.cpu().numpy()
         for i in range(B):
             np.testing.assert_array_equal(got[i, :rna[i]], want_all[i, :rna[i]])
             if rnv[i]:
-                v = fit(rf[i, :rnv[i]])
+                v = fit(rf[i, :rnv[i]], w32)
                 assert int(ba[i]) == int(np.argmax(v)) and float(bv[i]) == float(v.max())
             else:
                 assert int(ba[i]) == -1
@@ -967,18 +970,22 @@ class DirectedCases:
         db.check_boards(self.boards, R)
         desc = orc.make_desc(C, R, self.catalogue)
         n_valid = np.zeros((len(self.catalogue), len(self.boards)), np.int64)
+        n_clearing = np.zeros_like(n_valid)  # placements (terminal ones included) that complete a row
         self.n_rescued = 0
         for pi, name in enumerate(self.catalogue):
             for b in range(len(self.boards)):
                 out = orc.placements(desc, self.boards[b], name)
                 term = out["terminal"].astype(bool)
                 n_valid[pi, b] = int((~term).sum())
+                n_clearing[pi, b] = int((out["n_cleared"] > 0).sum())
                 if b < n_near_top:  # counted as mask_rescue_stress counts them
                     self.n_rescued += int(((out["anchor_row"] + 0 >= 0) & (~term) & (out["n_cleared"] > 0) &
                                            (out["heights"].max(axis=1) + out["n_cleared"] > R)).sum())
         self.n_valid_table = n_valid
+        self.n_clearing_table = n_clearing
         self.bix, self.pcs, self.act = db.expand(self.boards, n_valid)
         self.n_cases = len(self.bix)
+        self._after_ref = {}
 
     def padded(self, pad_to):
         """(bix, pcs, act) repeated cyclically to pad_to envs."""
@@ -987,6 +994,40 @@ class DirectedCases:
         assert pad_to >= self.n_cases
         ix = np.arange(pad_to) % self.n_cases
         return self.bix[ix], self.pcs[ix], self.act[ix]
+
+    AFTER_ORDERS = ("piece-major", "board-major")
+
+    def after_order(self, order):
+        """(bix, pcs) of the afterstate-family case list, one env per (board, catalogue piece) whether or not the piece
+        has a valid placement there: "piece-major" = whole wavefronts of one piece (narrow pieces alone in a wave),
+        "board-major" = env b * 9 + p (every wavefront mixes all nine pieces).  The first case is appended again
+        while the batch is even or a multiple of 64: the last lane pair then has one live lane and the last tile
+        is partial."""
+        nb, npc = len(self.boards), len(self.catalogue)
+        if order == "piece-major":
+            bix, pcs = np.tile(np.arange(nb), npc), np.repeat(np.arange(npc), nb)
+        else:
+            assert order == "board-major"
+            bix, pcs = np.repeat(np.arange(nb), npc), np.tile(np.arange(npc), nb)
+        while len(bix) % 2 == 0 or len(bix) % 64 == 0:
+            bix, pcs = np.append(bix, bix[0]), np.append(pcs, pcs[0])
+        return bix.astype(np.int64), pcs.astype(np.int64)
+
+    def after_reference(self, orc, order):
+        """The oracle's afterstate matrices of one order -- (feats, n_valid, feats_all, n_all), read-only -- computed
+        once and shared by the afterstate, greedy and rollout cases; also returns the oracle env they came from
+        (its boards and pieces stay as set here)."""
+        if order not in self._after_ref:
+            bix, pcs = self.after_order(order)
+            ref = orc.OracleVecEnv(self.C, self.R, len(bix), pieces=self.catalogue, auto_reset=False,
+                                   seed=AFTER_SEED, nthreads=0)
+            ref.cells[:] = self.boards[bix]
+            ref.piece[:] = pcs
+            out = ref.afterstates(include_terminal=True)
+            for x in out:
+                x.setflags(write=False)
+            self._after_ref[order] = (out, ref)
+        return self._after_ref[order]
 
 
 _DIRECTED = {}
@@ -1000,15 +1041,18 @@ def directed_cases(orc, C, R, n_near_top=60):
 
 
 class _Where:
-    """Names the env of a mismatch: geometry, env index, board family, piece, action(s)."""
+    """Names the env of a mismatch: geometry, env index, board family, piece, action(s) (act = None: the case has
+    no action -- the afterstate family looks at every placement of the env)."""
 
-    def __init__(self, cs, tag, bix, pcs, act):
+    def __init__(self, cs, tag, bix, pcs, act=None):
         self.cs, self.tag, self.bix, self.pcs, self.act = cs, tag, bix, pcs, act
         self.act2 = None
 
     def env(self, i):
-        s = "env %d: board %d (%s), piece %s, action %d" % (
-            i, self.bix[i], self.cs.names[self.bix[i]], self.cs.catalogue[self.pcs[i]], self.act[i])
+        s = "env %d: board %d (%s), piece %s" % (
+            i, self.bix[i], self.cs.names[self.bix[i]], self.cs.catalogue[self.pcs[i]])
+        if self.act is not None:
+            s += ", action %d" % self.act[i]
         if self.act2 is not None:
             s += ", then action %d" % self.act2[i]
         return s
@@ -1150,7 +1194,7 @@ def step_directed_boards(device, orc, C, R, n_near_top=60, pad_to=None):
 def step_many_directed_boards(device, orc, C, R, n_near_top=60, seed=21):
     """tetris_hip_step_many from the directed boards (device bag, auto-reset): three fused random-policy steps against
     three tetris_hip_step launches and the oracle, then two fused greedy steps from the same boards against
-    step(greedy_actions())."""
+    step(greedy_actions()) and the oracle, with the BCTS weights and again with the holes-only weights."""
     from tetris_amd import VecTetris
     cs = directed_cases(orc, C, R, n_near_top)
     bix, pcs, act = cs.padded(None)
@@ -1194,22 +1238,226 @@ def step_many_directed_boards(device, orc, C, R, n_near_top=60, seed=21):
     compare_state("after 3 random steps")
     assert a.stats() == b.stats() and a.stats()["invalid"] == 0
     assert (lines_seen[1:] > 0).all() and n_done > 0, (lines_seen, n_done)  # (from the oracle alone)
-    # greedy policy, from the same boards
-    inject()
-    w.tag = "step_many greedy B=%d" % B
-    out = a.step_many(2, policy="greedy")
-    for k in range(2):
-        ba, _ = b.greedy_actions()
-        played = torch.where(ba >= 0, ba, torch.zeros_like(ba))  # -1 = no valid action: play 0, as greedy_policy does
-        b.step(played.clone())
-        ref.step(played.cpu().numpy())
-        live = ref.invalid == 0
-        assert live.any()
-        when = "greedy policy, step %d" % (k + 1)
-        w.eq(out["action"][k], played, "action, fused vs greedy_actions, " + when, live)
-        for name, single, want in (("obs", b.obs, ref.obs), ("reward", b.reward, ref.reward), ("done", b.done, ref.done),
-                                   ("lines", b.lines, ref.lines), ("n_valid", b.n_valid, ref.n_valid),
-                                   ("piece", b.piece, ref.piece)):
-            w.eq(out[name][k], single, "%s, fused vs single step, %s" % (name, when), live)
-            w.eq(out[name][k], want, "%s, %s" % (name, when), live)
-    compare_state("after 2 greedy steps")
+    # greedy policy, from the same boards: the BCTS weights, then the holes-only weights, under which hundreds of envs
+    # have several actions of maximal fitness (the kernel's own copy of the first-maximum tie rule)
+    for wname, weights in (("BCTS", None), ("holes-only", HOLES_ONLY_WEIGHTS)):
+        inject()
+        w.tag = "step_many greedy (%s weights) B=%d" % (wname, B)
+        out = a.step_many(2, policy="greedy", weights=weights)
+        for k in range(2):
+            ba, _ = b.greedy_actions(weights=weights)
+            played = torch.where(ba >= 0, ba, torch.zeros_like(ba))  # -1 = no valid action: play 0, as greedy_policy does
+            b.step(played.clone())
+            ref.step(played.cpu().numpy())
+            live = ref.invalid == 0
+            assert live.any()
+            when = "greedy policy, step %d" % (k + 1)
+            w.eq(out["action"][k], played, "action, fused vs greedy_actions, " + when, live)
+            for name, single, want in (("obs", b.obs, ref.obs), ("reward", b.reward, ref.reward), ("done", b.done, ref.done),
+                                       ("lines", b.lines, ref.lines), ("n_valid", b.n_valid, ref.n_valid),
+                                       ("piece", b.piece, ref.piece)):
+                w.eq(out[name][k], single, "%s, fused vs single step, %s" % (name, when), live)
+                w.eq(out[name][k], want, "%s, %s" % (name, when), live)
+        compare_state("after 2 greedy steps (%s weights)" % wname)
+
+
+# ---- directed boards through the afterstate family -------------------------------------------------
+
+# The afterstate family (tetris_hip_afterstates, tetris_hip_policy_greedy, tetris_hip_rollouts: all on
+# tet::afterstates_env) has one kernel variant per word size x (packed planes with a compile-time chunk count | one
+# plane per column with the chunk count taken from R at run time) x column count; after_geometry_variant() states the
+# conditions and tests/test_host_logic.py checks every entry against what the library reports.
+AFTER_GEOMETRY_VARIANTS = [
+    # u32, packed planes (stored rows R + 4 <= 24), NCH = 2: every width, a one-chunk board, a chunk border inside
+    (("u32", "packed", 2), [(5, 20), (6, 20), (7, 20), (8, 20), (9, 20), (10, 20), (11, 20), (12, 20),
+                            (6, 4), (10, 4), (10, 13)]),
+    # u32, one plane per column, three 12-row chunks at run time (stored rows 25..31)
+    (("u32", "planes", 3), [(10, 21), (12, 24), (11, 27)]),
+    # u64, packed planes (stored rows 32..48), NCH = 4; 10x28 is the smallest 64-bit board
+    (("u64", "packed", 4), [(10, 28), (9, 40), (10, 40), (12, 40), (10, 44)]),
+    # u64, one plane per column: five chunks up to 60 stored rows, six beyond (10x56 | 10x57); the tallest boards
+    (("u64", "planes", 5), [(10, 45), (10, 56)]),
+    (("u64", "planes", 6), [(10, 57), (5, 59), (12, 59)]),
+]
+AFTER_GEOMETRIES = [g for _, gs in AFTER_GEOMETRY_VARIANTS for g in gs]
+ROLLOUT_GEOMETRIES = [(10, 20), (7, 20), (12, 20), (6, 4), (11, 27), (10, 40), (9, 40), (10, 45), (12, 59)]
+AFTER_SEED = 29  # device bag of the envs (only the rollouts draw from it)
+HOLES_ONLY_WEIGHTS = (0.0, 0.0, -1.0, 0.0, 0.0, 0.0, 0.0, 0.0)
+
+
+def after_geometry_variant(C, R):
+    """(word, board storage, 12-row chunks the afterstate walk reads per column) of a geometry, restated from
+    tetris_table.hpp (word size), tet::board_packed / packed_geometry (storage) and the chunk conditions of
+    col_own / col_wells_packed (k < NCH, or k < 2 || 12 k < R + 4 when NCH = 0)."""
+    stored = R + 4
+    word = "u32" if stored <= 31 else "u64"
+    bits = 32 if word == "u32" else 64
+    if stored <= bits * 3 // 4:
+        return word, "packed", 2 if word == "u32" else 4
+    return word, "planes", len([k for k in range((bits - 1 + 11) // 12) if 12 * k < bits - 1 and (k < 2 or 12 * k < stored)])
+
+
+def greedy_weight_vectors():
+    """(name, float32[8]): the BCTS weights; holes only (ties in the hundreds); all zeros (every valid action ties:
+    the first must win); one fixed draw of a normal vector."""
+    from tetris_amd import VecTetris
+    return [("BCTS", np.array(VecTetris.BCTS_WEIGHTS, np.float32)),
+            ("holes-only", np.array(HOLES_ONLY_WEIGHTS, np.float32)),
+            ("zeros", np.zeros(8, np.float32)),
+            ("normal", np.random.default_rng(20261019).normal(size=8).astype(np.float32))]
+
+
+def _best_of(rf, rnv, w32):
+    """First valid action of maximal fitness (-1: none), that maximum (0: none) and the number of valid actions that
+    reach it, from the oracle's valid matrix."""
+    k = np.arange(rf.shape[1])[None, :]
+    v = np.where(k < rnv[:, None], fit(rf, w32), -np.inf)
+    has = rnv > 0
+    top = v.max(axis=1)
+    best = np.where(has, v.argmax(axis=1), -1).astype(np.int32)
+    n_top = np.where(has, (v == top[:, None]).sum(axis=1), 0)
+    return best, np.where(has, top, 0).astype(np.float32), n_top
+
+
+def after_coverage(orc, C, R, n_near_top=60):
+    """Figures of the coverage conditions of the afterstate-family cases, from the oracle's outputs alone, asserted:
+    a case list that misses one of them would let a test pass by testing nothing."""
+    from tetris_amd import VecTetris
+    cs = directed_cases(orc, C, R, n_near_top)
+    if getattr(cs, "after_figures", None) is None:
+        (rf, rnv, rfa, rna), _ = cs.after_reference(orc, "board-major")
+        bix, pcs = cs.after_order("board-major")
+        tied = [int((_best_of(rf, rnv, np.array(w, np.float32))[2] > 1).sum())
+                for w in (VecTetris.BCTS_WEIGHTS, HOLES_ONLY_WEIGHTS)]
+        cs.after_figures = dict(
+            C=C, R=R, B=len(bix), n_valid_0=int((rnv == 0).sum()), n_valid_lt_n_all=int((rnv < rna).sum()),
+            line_clearing=int(cs.n_clearing_table[pcs, bix].sum()), pieces=len(np.unique(pcs)),
+            tied_bcts=tied[0], tied_holes_only=tied[1], max_feats=rfa.max(axis=(0, 1)).astype(int).tolist())
+        print("afterstate cases %dx%d: %s" % (C, R, cs.after_figures))
+    f = cs.after_figures
+    assert f["B"] % 2 == 1 and f["B"] % 64 != 0, f
+    assert f["n_valid_0"] >= 100 and f["n_valid_lt_n_all"] >= 500 and f["line_clearing"] >= 200, f
+    assert f["pieces"] == 9 and f["tied_bcts"] >= 30 and f["tied_holes_only"] >= 300, f
+    return f
+
+
+def afterstates_directed_boards(device, orc, C, R, n_near_top=60):
+    """tetris_hip_afterstates against the oracle from the directed boards, one env per (board, catalogue piece), in
+    two env orders through the SAME env object (its output buffers are reused: a row the second launch fails to zero
+    shows as stale data): both matrices and both counts whole-array bit-exact, the refresh kernel's n_valid, the
+    feats_all == NULL path, the action-major layout and the direct_by multiply."""
+    from tetris_amd import VecTetris
+    cs = directed_cases(orc, C, R, n_near_top)
+    figures = after_coverage(orc, C, R, n_near_top)
+    B = figures["B"]
+    env = VecTetris(C, R, B, device=device, pieces=cs.catalogue, seed=AFTER_SEED)
+    twin_am = VecTetris(C, R, B, device=device, pieces=cs.catalogue, seed=AFTER_SEED, afterstate_layout="action_major")
+    twin_dir = VecTetris(C, R, B, device=device, pieces=cs.catalogue, seed=AFTER_SEED, feature_directions=DIRS)
+    d32 = np.array(DIRS, np.float32)
+    for order in cs.AFTER_ORDERS:
+        bix, pcs = cs.after_order(order)
+        assert len(bix) == B
+        (rf, rnv, rfa, rna), _ = cs.after_reference(orc, order)
+        w = _Where(cs, "afterstates, %s B=%d" % (order, B), bix, pcs)
+        cells = cs.boards[bix]
+        env.set_boards(cells, pcs)
+        w.eq(env.n_valid, rnv, "n_valid of the refresh kernel")
+        f, nv, fa, na = env.get_after_states(include_terminal=True)
+        w.eq(nv, rnv, "n_valid")
+        w.eq(na, rna, "n_all")
+        w.eq(f, rf, "feats (zero rows included)")
+        w.eq(fa, rfa, "feats_all (zero rows included)")
+        # feats_all == NULL: the same valid matrix, written afresh (the buffer is poisoned in between)
+        f.fill_(float("nan"))
+        nv.fill_(255)
+        f2, nv2 = env.get_after_states()
+        w.eq(nv2, rnv, "n_valid without feats_all")
+        w.eq(f2, rf, "feats without feats_all")
+        w.tag = "afterstates action-major, %s B=%d" % (order, B)
+        twin_am.set_boards(cells, pcs)
+        f, nv, fa, na = twin_am.get_after_states(include_terminal=True)
+        assert f.shape == (B, env.a_max, 8) and not f.is_contiguous()
+        w.eq(nv, rnv, "n_valid")
+        w.eq(na, rna, "n_all")
+        w.eq(f, rf, "feats")
+        w.eq(fa, rfa, "feats_all")
+        w.tag = "afterstates feature_directions, %s B=%d" % (order, B)
+        twin_dir.set_boards(cells, pcs)
+        f, nv, fa, na = twin_dir.get_after_states(include_terminal=True)
+        w.eq(nv, rnv, "n_valid")
+        w.eq(na, rna, "n_all")
+        w.eq(f, rf * d32, "feats")
+        w.eq(fa, rfa * d32, "feats_all")
+    return figures
+
+
+def greedy_directed_boards(device, orc, C, R, n_near_top=60):
+    """tetris_hip_policy_greedy against the oracle on the same case lists under four weight vectors: fitness_all
+    bit-exact against fit() of the oracle's feats_all below n_all and zero beyond, best_action = the FIRST valid action
+    of maximal fitness (-1 and best_value 0 where there is none), best_value = that maximum."""
+    from tetris_amd import VecTetris
+    cs = directed_cases(orc, C, R, n_near_top)
+    figures = after_coverage(orc, C, R, n_near_top)
+    B = figures["B"]
+    env = VecTetris(C, R, B, device=device, pieces=cs.catalogue, seed=AFTER_SEED)
+    for order in cs.AFTER_ORDERS:
+        bix, pcs = cs.after_order(order)
+        (rf, rnv, rfa, rna), _ = cs.after_reference(orc, order)
+        env.set_boards(cs.boards[bix], pcs)
+        k = np.arange(rfa.shape[1])[None, :]
+        for wname, w32 in greedy_weight_vectors():
+            w = _Where(cs, "greedy, %s weights, %s B=%d" % (wname, order, B), bix, pcs)
+            want_all = np.where(k < rna[:, None], fit(rfa, w32), np.float32(0))
+            best, top, _ = _best_of(rf, rnv, w32)
+            ba, bv, fall = env.greedy_actions(weights=w32, include_fitness=True)
+            w.eq(fall, want_all, "fitness_all")
+            w.eq(ba, best, "best_action")
+            w.eq(bv, top, "best_value (0 where n_valid == 0)")
+            assert (best[rnv == 0] == -1).all() and (top[rnv == 0] == 0).all()
+            # fitness_all == NULL: the same answers, written afresh
+            ba.fill_(-7)
+            bv.fill_(float("nan"))
+            ba, bv = env.greedy_actions(weights=w32)
+            w.eq(ba, best, "best_action without fitness_all")
+            w.eq(bv, top, "best_value without fitness_all")
+    return figures
+
+
+ROLLOUT_SETTINGS = (("random", 4, 2, None), ("greedy", 3, 2, None), ("greedy", 3, 2, HOLES_ONLY_WEIGHTS))
+
+
+def rollouts_directed_boards(device, orc, C, R, n_near_top=60):
+    """tetris_hip_rollouts against the oracle from the board-major case list (every wavefront mixes envs, pieces and
+    first actions): random rollouts, greedy ones with the BCTS weights and with the holes-only weights (the tie rule
+    inside rollout_env); NaN pattern and values bit-identical, the envs untouched."""
+    from tetris_amd import VecTetris
+    cs = directed_cases(orc, C, R, n_near_top)
+    bix, pcs = cs.after_order("board-major")
+    B = len(bix)
+    (rf, rnv, rfa, rna), ref = cs.after_reference(orc, "board-major")
+    env = VecTetris(C, R, B, device=device, pieces=cs.catalogue, auto_reset=False, seed=AFTER_SEED)
+    env.set_boards(cs.boards[bix], pcs)
+    before = (env.cols.clone(), env.meta.clone())
+    cells_before, piece_before = ref.cells.copy(), ref.piece.copy()
+    figures = dict(C=C, R=R, B=B)
+    for policy, length, n, weights in ROLLOUT_SETTINGS:
+        name = "%s length=%d n=%d%s" % (policy, length, n, " holes-only" if weights is not None else "")
+        w = _Where(cs, "rollouts %s B=%d" % (name, B), bix, pcs)
+        kw = {} if weights is None else dict(weights=weights)
+        want = ref.rollouts(length=length, n=n, policy=policy, **kw)
+        # coverage, from the oracle alone
+        k = np.arange(want.shape[1])[None, :]
+        np.testing.assert_array_equal(np.isnan(want), k >= rnv[:, None])
+        v = want[~np.isnan(want)]
+        fig = dict(minus_one=int((v == -1).sum()), other=int((v != -1).sum()), distinct=len(np.unique(v)))
+        figures[name] = fig
+        print("rollout cases %dx%d %s: %s" % (C, R, name, fig))
+        assert fig["minus_one"] >= 1000 and fig["other"] >= 1000 and fig["distinct"] >= 6, (C, R, name, fig)
+        got = env.rollouts(length=length, n=n, policy=policy, **kw)
+        assert got.dtype == torch.float64
+        got = got.cpu().numpy()
+        w.eq(np.isnan(got), np.isnan(want), "NaN pattern of the returns")
+        w.eq(np.nan_to_num(got, nan=7.0), np.nan_to_num(want, nan=7.0), "returns")
+        assert torch.equal(env.cols, before[0]) and torch.equal(env.meta, before[1]), (C, R, name)
+    assert np.array_equal(ref.cells, cells_before) and np.array_equal(ref.piece, piece_before)
+    return figures

@@ -264,3 +264,22 @@ def test_step_directed_boards_large_tile(orc):
 @pytest.mark.parametrize("C,R", pc.STEP_MANY_GEOMETRIES)
 def test_step_many_directed_boards(orc, C, R):
     pc.step_many_directed_boards(DEV, orc, C, R)
+
+
+@pytest.mark.parametrize("C,R", pc.AFTER_GEOMETRIES)
+def test_afterstates_directed_boards(orc, C, R):
+    """tetris_hip_afterstates from the hand-built boards, one env per (board, piece), whole wavefronts of one piece and
+    wavefronts that mix all nine, against the oracle; one geometry per variant of the afterstate family."""
+    pc.afterstates_directed_boards(DEV, orc, C, R)
+
+
+@pytest.mark.parametrize("C,R", pc.AFTER_GEOMETRIES)
+def test_greedy_directed_boards(orc, C, R):
+    """tetris_hip_policy_greedy on the same cases under four weight vectors (BCTS, holes only, zeros, a normal draw):
+    fitness of every placement, the first maximum, its value."""
+    pc.greedy_directed_boards(DEV, orc, C, R)
+
+
+@pytest.mark.parametrize("C,R", pc.ROLLOUT_GEOMETRIES)
+def test_rollouts_directed_boards(orc, C, R):
+    pc.rollouts_directed_boards(DEV, orc, C, R)

@@ -151,3 +151,38 @@ def test_step_directed_boards_large_tile(host_backend, orc):
 @pytest.mark.parametrize("C,R", pc.STEP_MANY_GEOMETRIES)
 def test_step_many_directed_boards(host_backend, orc, C, R):
     pc.step_many_directed_boards(DEV, orc, C, R)
+
+
+def test_after_geometries_cover_every_variant(host_backend):
+    """The variant each entry of AFTER_GEOMETRIES is listed under is the one the library picks for it."""
+    from tetris_amd import VecTetris
+    seen = set()
+    for variant, geometries in pc.AFTER_GEOMETRY_VARIANTS:
+        for C, R in geometries:
+            assert pc.after_geometry_variant(C, R) == variant, (C, R)
+            env = VecTetris(C, R, 1, device=DEV)
+            assert env.desc.word_bytes == (4 if variant[0] == "u32" else 8), (C, R)
+            assert (env.n_planes < C) == (variant[1] == "packed"), (C, R, env.n_planes)
+            seen.add((variant, C))
+    assert {v for v, _ in seen} == {v for v, _ in pc.AFTER_GEOMETRY_VARIANTS}
+    assert {C for _, C in seen} == set(range(5, 13))
+    assert len(set(pc.AFTER_GEOMETRIES)) == len(pc.AFTER_GEOMETRIES)
+    # the rollout subset keeps one entry per (word, storage) variant
+    assert {pc.after_geometry_variant(C, R)[:2] for C, R in pc.ROLLOUT_GEOMETRIES} == \
+        {v[:2] for v, _ in pc.AFTER_GEOMETRY_VARIANTS}
+    assert set(pc.ROLLOUT_GEOMETRIES) <= set(pc.AFTER_GEOMETRIES) | set(pc.DIRECTED_GEOMETRIES)
+
+
+@pytest.mark.parametrize("C,R", pc.AFTER_GEOMETRIES)
+def test_afterstates_directed_boards(host_backend, orc, C, R):
+    pc.afterstates_directed_boards(DEV, orc, C, R)
+
+
+@pytest.mark.parametrize("C,R", pc.AFTER_GEOMETRIES)
+def test_greedy_directed_boards(host_backend, orc, C, R):
+    pc.greedy_directed_boards(DEV, orc, C, R)
+
+
+@pytest.mark.parametrize("C,R", pc.ROLLOUT_GEOMETRIES)
+def test_rollouts_directed_boards(host_backend, orc, C, R):
+    pc.rollouts_directed_boards(DEV, orc, C, R)
