@@ -46,7 +46,7 @@ int main() {
   const std::vector<int32_t> dflt = {4, 3}, std7 = {0, 7, 8, 1, 2, 5, 6};
   int rc = 0;
   for (int C : {10, 12, 11, 9, 5})
-    for (int R : {20, 40}) {
+    for (int R : {20, 24, 40, 45}) {  // NCH = 2, 0 (u32, one plane per column), 4, 0 (u64, one plane per column)
       rc |= run(C, R, dflt, 256);
       rc |= run(C, R, std7, 256);
     }

@@ -1263,6 +1263,19 @@ TET_HD float fitness_of(const float (&f)[8], const float (&w)[8]) {
   return acc;
 }
 
+// The greedy policy's choice among the valid placements of one env: the first row of maximal fitness
+// (game.py:102-120 on the non-terminal ones), whatever order the rows are offered in.
+struct GreedyPick {
+  float best = 0.f;
+  int best_row = -1;  // -1: nothing offered (the env is over)
+  TET_HD void offer(float v, int row) {
+    if (best_row < 0 || v > best || (v == best && row < best_row)) {
+      best = v;
+      best_row = row;
+    }
+  }
+};
+
 // ---- one env step (game.py:82-92) --------------------------------------------
 struct StepOut {
   float obs[8];
@@ -1397,19 +1410,11 @@ TET_HD int rollout_env(const W (&col0)[C], uint64_t meta0, int a0, int length, i
         use_policy = true;
         action = -1;
       } else {  // greedy: first non-terminal action of maximal fitness (game.py:102-120 on valid ones)
-        float best = 0.f;
-        int best_row = -1;
+        GreedyPick pick;
         afterstates_env<W, C, NCH>(col, meta, tab, hole_lut, R, [&](bool has, int, int, float (&f)[8], int, int row, bool is_valid) {
-          if (!has) return;
-          if (is_valid) {
-            const float v = fitness_of(f, w);
-            if (best_row < 0 || v > best || (v == best && row < best_row)) {
-              best = v;
-              best_row = row;
-            }
-          }
+          if (has && is_valid) pick.offer(fitness_of(f, w), row);
         });
-        action = best_row;
+        action = pick.best_row;
       }
     }
     StepOut out;

@@ -1,0 +1,231 @@
+// tetris_entry.hpp -- what a kernel of tetris_kernels.hip and the CPU entry of the same name in
+// tests/harness/core_host.cpp share beyond the lane logic of tetris_core.hpp: which template
+// instantiation runs for a geometry, the table blobs, and the per-env bodies that are not a step.
+// The kernels add what only a GPU needs (LDS staging, ballots, paired stores, launch bounds).
+#pragma once
+#include "tetris_core.hpp"
+#include "tetris_table.hpp"
+
+#ifndef TET_LUT10
+#define TET_LUT10 1   // 0: always the 12-row-chunk tables (A/B timing)
+#endif
+#if defined(__HIPCC__)
+#define TET_TABLE __device__ const
+#else
+#define TET_TABLE const
+#endif
+
+namespace {  // (one copy per translation unit, under the names the kernels' code objects have always carried)
+
+// feature tables (tools/gen_feature_lut.py): byte tables for hole depth and wells (28 KiB), copied
+// to LDS as one block by the kernels that compute features
+struct alignas(16) FeatureLut {
+  uint8_t bytes[tet::kFeatureLutBytes];
+};
+TET_TABLE FeatureLut kFeatureLut = {{
+#include "tetris_feature_lut.inc"
+}};
+static_assert(sizeof(FeatureLut) == tet::kFeatureLutBytes, "layout assumed by col_wells");
+// the same tables for 10-row chunks (7 KiB): stepping kernels on boards of up to 20 rows
+struct alignas(16) FeatureLut10 {
+  uint8_t bytes[tet::kFeatureLut10Bytes];
+};
+TET_TABLE FeatureLut10 kFeatureLut10 = {{
+#include "tetris_feature_lut10.inc"
+}};
+// tables of the kernels that walk the afterstates (tet::AfterLut: hole tables, packed wells entries, select tables)
+struct alignas(16) AfterLutData {
+  uint8_t bytes[tet::kAfterLutBytes];
+};
+TET_TABLE AfterLutData kAfterLut = {{
+#include "tetris_after_lut.inc"
+}};
+
+}  // namespace
+
+namespace tet {
+
+template <bool V> struct BoolConst { static constexpr bool value = V; };
+
+// Where a hot kernel (step, step_many, rollouts) still writes one of the small bodies below out itself,
+// sharing it moved the kernel's device code (operand order, register allocation), and that code is held
+// fixed; the text there is the same rule and the CPU entry calls the function here.
+
+// ---- kernel variant of a geometry ---------------------------------------------------------------
+// Packed boards (tet::board_packed: stored rows within three quarters of the word) always run the
+// variants with a compile-time chunk count -- NCH = 2 on u32, 4 on u64 -- and those variants read /
+// write the packed planes; everything else is NCH = 0 on one plane per column.
+template <typename W>
+inline bool packed_geometry(int R) { return R + 4 <= 6 * (int)sizeof(W); }  // == tet::board_packed (TET_NO_PACK builds keep the variant choice)
+template <typename W>
+constexpr int packed_chunks() { return sizeof(W) == 4 ? 2 : 4; }
+
+// The ONE place that turns (W, R) into template arguments: f(IntConst<NCH>, IntConst<CR>, BoolConst<PACK>).
+// The stepping kernels take (NCH, CR), the afterstate family NCH (its tables are the 12-row AfterLut), reset
+// and refresh PACK.  CR: a step only evaluates the features of a NON-terminal board (cells below row R): up to
+// R = 20 (u32) two 10-row chunks cover it, up to R = 40 (u64) four, and the tables are the 7 KiB set;
+// otherwise 12-row chunks.
+template <typename W, typename F>
+inline void kernel_variant(int R, F&& f) {
+  constexpr int N = packed_chunks<W>();
+  if (!packed_geometry<W>(R)) f(IntConst<0>{}, IntConst<12>{}, BoolConst<false>{});
+  else if (R <= 10 * N && TET_LUT10) f(IntConst<N>{}, IntConst<10>{}, BoolConst<!TET_NO_PACK>{});
+  else f(IntConst<N>{}, IntConst<12>{}, BoolConst<!TET_NO_PACK>{});
+}
+
+// ---- a step's configuration -----------------------------------------------------------------------
+inline void fill_step_cfg(StepCfg& cfg, const TetrisDesc* desc, int auto_reset, bool compute_obs) {
+  cfg.R = desc->num_rows;
+  cfg.n_pieces = desc->n_pieces;
+  cfg.auto_reset = auto_reset;
+  cfg.compute_obs = compute_obs;
+  cfg.has_direct_by = desc->has_direct_by;
+  for (int i = 0; i < 8; ++i) cfg.direct_by[i] = desc->direct_by[i];
+}
+// the two keys of step `step_idx` (four counters per step: + 2 is the reset's, + 1 is free)
+TET_HD void step_keys(uint64_t seed, uint64_t step_idx, StepCfg& cfg) {
+  cfg.key_step = hash_key(seed, step_idx * 4u + 0u);
+  cfg.key_policy = hash_key(seed, step_idx * 4u + 3u);
+}
+
+// ---- replay stream ------------------------------------------------------------------------------
+// What env i of B reads for one step from `stream` ([stream_len][B] piece indices, NULL: none) at its
+// cursor: the piece of the step draw and of the reset draw.  A step consumes one row, two when it
+// ends the episode under auto-reset: an env whose stream cannot cover that is `exhausted` -- counted
+// as invalid and left untouched (never a silent replay of the last row).
+TET_HD void stream_read(const uint8_t* stream, const int32_t* cursors, int64_t stream_len, int64_t B, int64_t i,
+                        const StepCfg& cfg, int& draw, int& draw_reset, int& cursor, bool& exhausted) {
+  draw = -1;
+  draw_reset = -1;
+  cursor = 0;
+  exhausted = false;
+  if (stream) {
+    cursor = cursors[i];
+    exhausted = (int64_t)cursor + (cfg.auto_reset ? 2 : 1) > stream_len || cursor < 0;
+    int64_t r0 = cursor < stream_len ? cursor : stream_len - 1;
+    int64_t r1 = cursor + 1 < stream_len ? cursor + 1 : stream_len - 1;
+    draw = stream[r0 * B + i];
+    draw_reset = stream[r1 * B + i];
+  }
+}
+// the cursor after a step that was not invalid
+TET_HD int stream_advance(int cursor, const StepOut& out, const StepCfg& cfg) {
+  return cursor + 1 + ((out.done && cfg.auto_reset) ? 1 : 0);
+}
+// a reset consumes one row: an env whose cursor is at or past the end is left untouched and counted
+// as invalid (as the step does), never continued on the last row
+TET_HD bool stream_reset_exhausted(int cursor, int64_t stream_len) { return cursor < 0 || cursor >= stream_len; }
+
+// ---- reset / refresh of one env -------------------------------------------------------------------
+// game.py:53-63: empty board, a piece from the stream row at `cursor` or from the (fresh or kept) bag
+template <typename W, int C, bool PACK>
+TET_HD void reset_env(W* cols, uint64_t* meta, int64_t B, int64_t i, const SetTable& tab, int init_bag, int n_pieces,
+                      uint32_t key, int64_t env_offset, const uint8_t* stream, int32_t* cursors, int cursor,
+                      uint8_t* piece_out, uint8_t* n_valid_out) {
+#pragma unroll
+  for (int q = 0; q < n_planes(C, PACK); ++q) cols[plane_index(i, q, n_planes(C, PACK))] = 0;  // game.py:55-58
+  uint32_t bag = init_bag ? 0u : meta_bag(meta[i]);
+  int piece;
+  if (stream) {
+    piece = stream[(int64_t)cursor * B + i];
+    cursors[i] = cursor + 1;
+  } else {
+    piece = bag_draw(bag, n_pieces, hash_env(key, (uint32_t)(env_offset + i)) >> 16);  // game.py:60
+  }
+  const uint64_t mask = tab.fullmask[piece];
+  meta[i] = meta_pack(mask, piece, bag);
+  if (piece_out) piece_out[i] = (uint8_t)piece;
+  if (n_valid_out) n_valid_out[i] = (uint8_t)popc(mask);
+}
+
+// the valid mask of env i's board for the piece its control word names, recomputed
+template <typename W, int C, bool PACK>
+TET_HD void refresh_env(const W* cols, uint64_t* meta, uint8_t* n_valid_out, int64_t B, int64_t i, const SetTable& tab,
+                        int R) {
+  W col[C];
+  int h[C];
+  load_board<W, C, PACK>(cols, B, i, col);
+  heights_of<W, C>(col, h);
+  const uint64_t m = meta[i];
+  const int piece = meta_piece(m);
+  const uint64_t mask = valid_mask<W, C>(col, h, piece_entries(tab, piece), tab.fullmask[piece], R);
+  meta[i] = meta_pack(mask, piece, meta_bag(m));
+  if (n_valid_out) n_valid_out[i] = (uint8_t)popc(mask);
+}
+
+// ---- rollout fan-out ------------------------------------------------------------------------------
+// Mean return of the n rollouts of (env i, first action a0); NaN where a0 is not an action of the env.
+// Rollout r has the global id uid (its low word keys the hashes, its high word the key) and reads its
+// fed pieces, if any, from pieces[i][a0][r][0 .. length).
+template <typename W, int C, int NCH>
+TET_HD double rollout_mean(const W (&col)[C], uint64_t meta, int64_t i, int a0, int64_t env_offset, int a_max, int n,
+                           int length, int policy, const float (&w)[8], const SetTable& tab, const uint8_t* lut,
+                           W* scratch, int sstride, int R, int n_pieces, uint32_t key, const uint8_t* pieces) {
+  const int nv = popc(meta_mask(meta));
+  double mean = __builtin_nan("");
+  if (a0 < nv) {
+    int sum = 0;
+    for (int r = 0; r < n; ++r) {
+      const uint64_t uid = ((uint64_t)(env_offset + i) * (uint64_t)a_max + (uint64_t)a0) * (uint64_t)n + r;
+      const uint32_t key0 = mix32(key ^ ((uint32_t)(uid >> 32) * 0x9E3779B1u));
+      const uint64_t fed = ((uint64_t)(i * a_max + a0) * (uint64_t)n + (uint64_t)r) * (uint64_t)length;
+      sum += rollout_env<W, C, NCH>(col, meta, a0, length, policy, w, tab, lut, scratch, sstride, R, n_pieces, key0,
+                                    (uint32_t)uid, pieces ? pieces + fed : nullptr);
+    }
+    mean = (double)sum / (double)n;
+  }
+  return mean;
+}
+
+// ---- the reference's piece sampler on NumPy's legacy global stream ----------------------------------
+// (tetromino.py:12-22 on top of np.random.seed / np.random.permutation): env i is
+// seeded like `np.random.seed(seeds[i])` right before `game.Tetris(...)` is constructed, and row t of
+// the stream is the list index its sampler hands out at its t-th call.  MT19937 (Matsumoto &
+// Nishimura) with NumPy's init_genrand seeding; permutation(n) = Fisher-Yates from the top with
+// masked rejection sampling on raw 32-bit outputs.  The 2.5 KB generator state is private to the env.
+TET_HD void numpy_bag_stream_env(const uint32_t* seeds, int n_pieces, int64_t L, uint8_t* stream, int64_t B, int64_t i) {
+  uint32_t mt[624];
+  mt[0] = seeds[i];
+  for (int k = 1; k < 624; ++k) mt[k] = 1812433253U * (mt[k - 1] ^ (mt[k - 1] >> 30)) + (uint32_t)k;
+  int pos = 624;
+  auto next_u32 = [&]() -> uint32_t {
+    if (pos >= 624) {
+      for (int k = 0; k < 624; ++k) {
+        const uint32_t y = (mt[k] & 0x80000000U) | (mt[k + 1 < 624 ? k + 1 : 0] & 0x7fffffffU);
+        mt[k] = mt[k + 397 < 624 ? k + 397 : k + 397 - 624] ^ (y >> 1) ^ ((y & 1U) ? 0x9908b0dfU : 0U);
+      }
+      pos = 0;
+    }
+    uint32_t y = mt[pos++];
+    y ^= y >> 11;
+    y ^= (y << 7) & 0x9d2c5680U;
+    y ^= (y << 15) & 0xefc60000U;
+    y ^= y >> 18;
+    return y;
+  };
+  uint8_t bag[TETRIS_MAX_PIECES];
+  int left = 0;
+  for (int64_t t = 0; t < L; ++t) {
+    if (left == 0) {  // tetromino.py:15,18-19: a fresh np.random.permutation(n)
+      for (int k = 0; k < n_pieces; ++k) bag[k] = (uint8_t)k;
+      for (int k = n_pieces - 1; k >= 1; --k) {
+        uint32_t mask = (uint32_t)k;
+        mask |= mask >> 1;
+        mask |= mask >> 2;
+        mask |= mask >> 4;
+        uint32_t v;
+        do {
+          v = next_u32() & mask;
+        } while (v > (uint32_t)k);
+        const uint8_t tmp = bag[k];
+        bag[k] = bag[v];
+        bag[v] = tmp;
+      }
+      left = n_pieces;
+    }
+    stream[t * B + i] = bag[n_pieces - left];  // tetromino.py:20-21: element 0, then delete it
+    --left;
+  }
+}
+
+}  // namespace tet

@@ -10,8 +10,7 @@
 #include <string.h>
 
 #include "../../include/tetris_hip.h"
-#include "tetris_core.hpp"
-#include "tetris_table.hpp"
+#include "tetris_entry.hpp"
 
 namespace {
 
@@ -42,9 +41,6 @@ constexpr int step_waves() { return TET_STEP_WAVES ? TET_STEP_WAVES : (sizeof(W)
 #ifndef TET_STEP_BLOCK
 #define TET_STEP_BLOCK 0
 #endif
-#ifndef TET_LUT10
-#define TET_LUT10 1   // 0: always the 12-row-chunk tables (A/B timing)
-#endif
 template <typename W>
 constexpr int step_block() { return TET_STEP_BLOCK ? TET_STEP_BLOCK : (sizeof(W) == 4 ? 512 : 256); }
 
@@ -64,29 +60,7 @@ __device__ uint64_t g_stamps[kStampWgs * kStampWords];
 
 // ---- kernels ------------------------------------------------------------------
 
-// feature tables (tools/gen_feature_lut.py): byte tables for hole depth and wells (28 KiB), copied
-// to LDS as one block by the kernels that compute features
-struct alignas(16) FeatureLut {
-  uint8_t bytes[tet::kFeatureLutBytes];
-};
-__device__ const FeatureLut kFeatureLut = {{
-#include "tetris_feature_lut.inc"
-}};
-static_assert(sizeof(FeatureLut) == tet::kFeatureLutBytes, "layout assumed by col_wells");
-// the same tables for 10-row chunks (7 KiB): stepping kernels on boards of up to 20 rows
-struct alignas(16) FeatureLut10 {
-  uint8_t bytes[tet::kFeatureLut10Bytes];
-};
-__device__ const FeatureLut10 kFeatureLut10 = {{
-#include "tetris_feature_lut10.inc"
-}};
-// tables of the kernels that walk the afterstates (tet::AfterLut: hole tables, packed wells entries, select tables)
-struct alignas(16) AfterLutData {
-  uint8_t bytes[tet::kAfterLutBytes];
-};
-__device__ const AfterLutData kAfterLut = {{
-#include "tetris_after_lut.inc"
-}};
+// the table blobs (kFeatureLut, kFeatureLut10, kAfterLut: tetris_entry.hpp) are copied to LDS as one block each
 static_assert(tet::kAfterLutBytes % 16 == 0, "staged as uint4");
 template <int CR>
 __device__ __forceinline__ const uint4* feature_lut_src() {
@@ -230,20 +204,7 @@ __device__ __forceinline__ void load_inputs(const StepParams& p, uint32_t i, Ste
   tet::unpack_board<W, C, PACK>(w, in.col);
   in.meta = ld_off(p.meta, ii * 8u);
   in.action = p.action ? ld_off(p.action, ii * 4u) : -1;
-  in.draw = -1;
-  in.draw_reset = -1;
-  in.cursor = 0;
-  in.exhausted = false;
-  if (p.stream) {
-    in.cursor = p.cursor[ii];
-    // a step consumes one row, two when it ends the episode under auto-reset: an env whose stream
-    // cannot cover that is counted as invalid and left untouched (never a silent replay of the last row)
-    in.exhausted = (int64_t)in.cursor + (p.cfg.auto_reset ? 2 : 1) > p.stream_len || in.cursor < 0;
-    int64_t r0 = in.cursor < p.stream_len ? in.cursor : p.stream_len - 1;
-    int64_t r1 = in.cursor + 1 < p.stream_len ? in.cursor + 1 : p.stream_len - 1;
-    in.draw = p.stream[r0 * p.B + ii];
-    in.draw_reset = p.stream[r1 * p.B + ii];
-  }
+  tet::stream_read(p.stream, p.cursor, p.stream_len, p.B, ii, p.cfg, in.draw, in.draw_reset, in.cursor, in.exhausted);
   in.status = make_uint4(0, 0, 0, 0);
   if (p.status) in.status = ld_off(reinterpret_cast<const uint4*>(p.status), (i >> 6) * 16u);  // this wave's slot
 }
@@ -303,7 +264,7 @@ __global__ __launch_bounds__(BLK, (step_waves<W, CR>())) void step_kernel(const 
     const uint64_t c = *p.step_counter;
     const uint64_t idx = (((uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)(c >> 32)) << 32) |
                           __builtin_amdgcn_readfirstlane((uint32_t)c)) + p.step_rel;
-    cfg.key_step = tet::hash_key(p.seed, idx * 4u + 0u);
+    cfg.key_step = tet::hash_key(p.seed, idx * 4u + 0u);  // (== tet::step_keys, written out: tetris_entry.hpp)
     cfg.key_policy = tet::hash_key(p.seed, idx * 4u + 3u);
   }
   int invalid = 0, done = 0, lines = 0, done_flag = 0;
@@ -324,7 +285,7 @@ __global__ __launch_bounds__(BLK, (step_waves<W, CR>())) void step_kernel(const 
       st_off(p.meta, i * 8u, in.meta);
       done = out.done;
       lines = out.lines;
-      if (p.stream) p.cursor[i] = in.cursor + 1 + ((out.done && cfg.auto_reset) ? 1 : 0);
+      if (p.stream) p.cursor[i] = in.cursor + 1 + ((out.done && cfg.auto_reset) ? 1 : 0);  // (== tet::stream_advance)
     }
     done_flag = out.done;  // what the done array holds (an env that was already over reports done again)
     st_off(p.reward, i * 4u, (int32_t)out.reward);
@@ -432,13 +393,13 @@ __global__ __launch_bounds__(step_block<W>(), (POLICY == 0 ? step_waves<W, CR>()
   StepCfg cfg = p.cfg;
 #pragma unroll 1
   for (int k = 0; k < q.n_steps; ++k) {
-    cfg.key_step = tet::hash_key(q.seed, (q.step_idx0 + (uint64_t)k) * 4u + 0u);
+    cfg.key_step = tet::hash_key(q.seed, (q.step_idx0 + (uint64_t)k) * 4u + 0u);  // (== tet::step_keys)
     cfg.key_policy = tet::hash_key(q.seed, (q.step_idx0 + (uint64_t)k) * 4u + 3u);
     int invalid = 0, done = 0, lines = 0;
     if (live) {
       int action = -1;
       bool use_policy = true;
-      if (POLICY == 1) {  // greedy: first non-terminal action of maximal fitness
+      if (POLICY == 1) {  // greedy: first non-terminal action of maximal fitness (== tet::GreedyPick)
         float best = 0.f;
         int best_row = -1;
         tet::afterstates_env<W, C, NCH>(in.col, in.meta, tab, hole_lut, cfg.R, [&](bool has, int, int, float (&f)[8], int, int row, bool is_valid) {
@@ -519,30 +480,15 @@ __global__ __launch_bounds__(kBlock) void reset_kernel(const ResetParams p) {
   stage_table(tab, p.tab);
   const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   const bool mine = i < p.B && !(p.reset_mask && !p.reset_mask[i]);
-  // replay mode: a reset consumes one stream row; an env whose cursor is at or past the end is left
-  // untouched and counted as invalid (as tetris_hip_step does), never continued on the last row
   const int cur = (mine && p.stream) ? p.cursor[i] : 0;
-  const bool exhausted = mine && p.stream && (cur < 0 || cur >= p.stream_len);
+  const bool exhausted = mine && p.stream && tet::stream_reset_exhausted(cur, p.stream_len);
   if (p.status) {
     const unsigned n_bad = (unsigned)__popcll(__ballot(exhausted));
     if ((threadIdx.x & 63) == 0 && n_bad) p.status[(i >> 6) * 4 + TETRIS_STATUS_INVALID] += n_bad;
   }
   if (!mine || exhausted) return;
-  W* cols = static_cast<W*>(p.cols);
-#pragma unroll
-  for (int q = 0; q < tet::n_planes(C, PACK); ++q) cols[tet::plane_index(i, q, tet::n_planes(C, PACK))] = 0;  // game.py:55-58
-  uint32_t bag = p.init_bag ? 0u : tet::meta_bag(p.meta[i]);
-  int piece;
-  if (p.stream) {
-    piece = p.stream[(int64_t)cur * p.B + i];
-    p.cursor[i] = cur + 1;
-  } else {
-    piece = tet::bag_draw(bag, p.n_pieces, tet::hash_env(p.key, (uint32_t)(p.env_offset + i)) >> 16);  // game.py:60
-  }
-  const uint64_t mask = tab.fullmask[piece];
-  p.meta[i] = tet::meta_pack(mask, piece, bag);
-  if (p.piece_out) p.piece_out[i] = (uint8_t)piece;
-  if (p.n_valid_out) p.n_valid_out[i] = (uint8_t)tet::popc(mask);
+  tet::reset_env<W, C, PACK>(static_cast<W*>(p.cols), p.meta, p.B, i, tab, p.init_bag, p.n_pieces, p.key, p.env_offset, p.stream,
+                             p.cursor, cur, p.piece_out, p.n_valid_out);
 }
 
 struct RefreshParams {
@@ -560,16 +506,7 @@ __global__ __launch_bounds__(kBlock) void refresh_kernel(const RefreshParams p) 
   stage_table(tab, p.tab);
   const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   if (i >= p.B) return;
-  const W* cols = static_cast<const W*>(p.cols);
-  W col[C];
-  int h[C];
-  tet::load_board<W, C, PACK>(cols, p.B, i, col);
-  tet::heights_of<W, C>(col, h);
-  const uint64_t meta = p.meta[i];
-  const int piece = tet::meta_piece(meta);
-  const uint64_t mask = tet::valid_mask<W, C>(col, h, tet::piece_entries(tab, piece), tab.fullmask[piece], p.R);
-  p.meta[i] = tet::meta_pack(mask, piece, tet::meta_bag(meta));
-  if (p.n_valid_out) p.n_valid_out[i] = (uint8_t)tet::popc(mask);
+  tet::refresh_env<W, C, PACK>(static_cast<const W*>(p.cols), p.meta, p.n_valid_out, p.B, i, tab, p.R);
 }
 
 struct AfterParams {
@@ -728,23 +665,17 @@ __global__ __launch_bounds__(kBlock, (after_waves<W, C>(TET_GREEDY_WAVES))) void
   const uint64_t full = tab.fullmask[piece];
   const uint64_t valid = tet::meta_mask(meta) & full;
   float* fall = p.fitness_all ? p.fitness_all + i * (int64_t)p.a_max : nullptr;
-  float best = 0.f;
-  int best_row = -1;
+  tet::GreedyPick pick;
   tet::afterstates_env<W, C, NCH>(col, meta, tab, hole_lut, p.R, [&](bool has, int, int, float (&f)[8], int row_all, int row, bool is_valid) {
     if (!has) return;
     const float v = tet::fitness_of(f, p.w);
     if (fall && !(TET_ABLATE & 2048)) fall[row_all] = v;
-    if (is_valid) {
-      if (best_row < 0 || v > best || (v == best && row < best_row)) {
-        best = v;
-        best_row = row;
-      }
-    }
+    if (is_valid) pick.offer(v, row);
   });
   if (fall)
     for (int k = tet::popc(full); k < p.a_max; ++k) fall[k] = 0.f;
-  p.best_action[i] = best_row;
-  if (p.best_value) p.best_value[i] = best;
+  p.best_action[i] = pick.best_row;
+  if (p.best_value) p.best_value[i] = pick.best;
 }
 
 struct RolloutParams {
@@ -786,6 +717,7 @@ __global__ __launch_bounds__(kRolloutBlock, (after_waves<W, C>(TET_STEP_GREEDY_W
   W col[C];
   tet::load_board<W, C, (NCH != 0 && !TET_NO_PACK)>(cols, p.B, i, col);
   const uint64_t meta = p.meta[i];
+  // (== tet::rollout_mean, written out: tetris_entry.hpp)
   const int nv = tet::popc(tet::meta_mask(meta));
   double mean = __longlong_as_double(0x7FF8000000000000ll);  // NaN: not an action of this env
   if (a0 < nv) {
@@ -822,60 +754,13 @@ __global__ __launch_bounds__(kBlock) void policy_random_kernel(const uint8_t* __
   action[i] = tet::policy_random(key, (uint32_t)(env_offset + i), n_valid[i]);
 }
 
-// The reference's piece sampler on NumPy's legacy global stream, reproduced on the device
-// (tetromino.py:12-22 on top of np.random.seed / np.random.permutation): env i is
-// seeded like `np.random.seed(seeds[i])` right before `game.Tetris(...)` is constructed, and row t of
-// the stream is the list index its sampler hands out at its t-th call.  MT19937 (Matsumoto &
-// Nishimura) with NumPy's init_genrand seeding; permutation(n) = Fisher-Yates from the top with
-// masked rejection sampling on raw 32-bit outputs.  One lane per env, the 2.5 KB generator state in
-// private memory: this is a set-up kernel for exact replays of seeded reference games (small to
-// moderate B), not a hot path -- the counter-based bag in `meta` is the one for large batches.
+// tet::numpy_bag_stream_env, one lane per env with the generator state in private memory: this is a set-up
+// kernel for exact replays of seeded reference games (small to moderate B), not a hot path -- the
+// counter-based bag in `meta` is the one for large batches.
 __global__ __launch_bounds__(64) void numpy_bag_stream_kernel(const uint32_t* __restrict__ seeds, int n_pieces,
                                                              int64_t L, uint8_t* __restrict__ stream, int64_t B) {
   const int64_t i = (int64_t)blockIdx.x * 64 + threadIdx.x;
-  if (i >= B) return;
-  uint32_t mt[624];
-  mt[0] = seeds[i];
-  for (int k = 1; k < 624; ++k) mt[k] = 1812433253U * (mt[k - 1] ^ (mt[k - 1] >> 30)) + (uint32_t)k;
-  int pos = 624;
-  auto next_u32 = [&]() -> uint32_t {
-    if (pos >= 624) {
-      for (int k = 0; k < 624; ++k) {
-        const uint32_t y = (mt[k] & 0x80000000U) | (mt[k + 1 < 624 ? k + 1 : 0] & 0x7fffffffU);
-        mt[k] = mt[k + 397 < 624 ? k + 397 : k + 397 - 624] ^ (y >> 1) ^ ((y & 1U) ? 0x9908b0dfU : 0U);
-      }
-      pos = 0;
-    }
-    uint32_t y = mt[pos++];
-    y ^= y >> 11;
-    y ^= (y << 7) & 0x9d2c5680U;
-    y ^= (y << 15) & 0xefc60000U;
-    y ^= y >> 18;
-    return y;
-  };
-  uint8_t bag[TETRIS_MAX_PIECES];
-  int left = 0;
-  for (int64_t t = 0; t < L; ++t) {
-    if (left == 0) {  // tetromino.py:15,18-19: a fresh np.random.permutation(n)
-      for (int k = 0; k < n_pieces; ++k) bag[k] = (uint8_t)k;
-      for (int k = n_pieces - 1; k >= 1; --k) {
-        uint32_t mask = (uint32_t)k;
-        mask |= mask >> 1;
-        mask |= mask >> 2;
-        mask |= mask >> 4;
-        uint32_t v;
-        do {
-          v = next_u32() & mask;
-        } while (v > (uint32_t)k);
-        const uint8_t tmp = bag[k];
-        bag[k] = bag[v];
-        bag[v] = tmp;
-      }
-      left = n_pieces;
-    }
-    stream[t * B + i] = bag[n_pieces - left];  // tetromino.py:20-21: element 0, then delete it
-    --left;
-  }
+  if (i < B) tet::numpy_bag_stream_env(seeds, n_pieces, L, stream, B, i);
 }
 
 template <typename W>
@@ -922,97 +807,76 @@ inline dim3 step_grid(int64_t B) { return dim3((unsigned)((B + step_block<W>() -
 // in parallel, and links the objects.  Compiled alone with neither macro the file is a complete
 // single-unit library (what the tools' experiment builds do).
 template <template <typename, int> class Launcher> struct LaunchId;
-// Kernel variant of a geometry.  Packed boards (tet::board_packed: stored rows within three
-// quarters of the word) always run the variants with a compile-time chunk count -- NCH = 2 on u32,
-// 4 on u64 -- and those variants read / write the packed planes; everything else is NCH = 0 on
-// one plane per column.
-template <typename W>
-inline bool packed_geometry(int R) { return R + 4 <= 6 * (int)sizeof(W); }  // == tet::board_packed (TET_NO_PACK builds keep the variant choice)
-template <typename W>
-constexpr int packed_chunks() { return sizeof(W) == 4 ? 2 : 4; }
-
+// Which instantiation a geometry runs is tet::kernel_variant's choice (tetris_entry.hpp), for these launchers as
+// for the CPU harness; only the tile size of the step kernel is decided here.
 template <typename W, int C>
 struct LaunchStep {
   static void run(const StepParams& p, hipStream_t s) {
-    // a step only evaluates the features of a NON-terminal board (cells below row R): up to R = 20
-    // (u32) two 10-row chunks cover it, up to R = 40 (u64) four, and the tables are the 7 KiB
-    // set; otherwise 12-row chunks
-    constexpr int N = packed_chunks<W>();
-    if (!packed_geometry<W>(p.cfg.R))
-      hipLaunchKernelGGL((step_kernel<W, C, 0, 12>), step_grid<W>(p.B), dim3(step_block<W>()), 0, s, p);
-    else if (p.cfg.R <= 10 * N && TET_LUT10) {
+    tet::kernel_variant<W>(p.cfg.R, [&](auto nch, auto cr, auto) {
+      constexpr int NCH = decltype(nch)::value, CR = decltype(cr)::value;
       // small batches (up to one wave per SIMD): 256-env tiles put a workgroup on every CU at 65,536 envs
       // and shorten its table staging: 6.75 us against 7.24 us per step there; 5 % slower at 131,072 envs, 1 % at
       // 1 Mi envs and beyond (profiles/r03_experiments/small_batch_variants.txt)
-      if (step_block<W>() > 256 && p.B <= kSmallBatch)
-        hipLaunchKernelGGL((step_kernel<W, C, N, 10, 256>), dim3((p.B + 255) / 256), dim3(256), 0, s, p);
-      else
-        hipLaunchKernelGGL((step_kernel<W, C, N, 10>), step_grid<W>(p.B), dim3(step_block<W>()), 0, s, p);
-    } else
-      hipLaunchKernelGGL((step_kernel<W, C, N, 12>), step_grid<W>(p.B), dim3(step_block<W>()), 0, s, p);
+      if constexpr (CR == 10 && step_block<W>() > 256) {
+        if (p.B <= kSmallBatch) {
+          hipLaunchKernelGGL((step_kernel<W, C, NCH, CR, 256>), dim3((p.B + 255) / 256), dim3(256), 0, s, p);
+          return;
+        }
+      }
+      hipLaunchKernelGGL((step_kernel<W, C, NCH, CR>), step_grid<W>(p.B), dim3(step_block<W>()), 0, s, p);
+    });
   }
 };
 template <typename W, int C>
 struct LaunchStepMany {
   static void run(const StepManyParams& q, hipStream_t s) {
-    constexpr int N = packed_chunks<W>();
-    const int R = q.one.cfg.R;
-    const bool packed = packed_geometry<W>(R);
-    if (q.policy == 1 && packed)
-      hipLaunchKernelGGL((step_many_kernel<W, C, N, 1, 12>), step_grid<W>(q.one.B), dim3(step_block<W>()), 0, s, q);
-    else if (q.policy == 1)
-      hipLaunchKernelGGL((step_many_kernel<W, C, 0, 1, 12>), step_grid<W>(q.one.B), dim3(step_block<W>()), 0, s, q);
-    else if (!packed)
-      hipLaunchKernelGGL((step_many_kernel<W, C, 0, 0, 12>), step_grid<W>(q.one.B), dim3(step_block<W>()), 0, s, q);
-    else if (R <= 10 * N && TET_LUT10)
-      hipLaunchKernelGGL((step_many_kernel<W, C, N, 0, 10>), step_grid<W>(q.one.B), dim3(step_block<W>()), 0, s, q);
-    else
-      hipLaunchKernelGGL((step_many_kernel<W, C, N, 0, 12>), step_grid<W>(q.one.B), dim3(step_block<W>()), 0, s, q);
+    tet::kernel_variant<W>(q.one.cfg.R, [&](auto nch, auto cr, auto) {
+      constexpr int NCH = decltype(nch)::value, CR = decltype(cr)::value;
+      if (q.policy == 1)  // the greedy policy evaluates terminal afterstates too: the afterstate family's tables
+        hipLaunchKernelGGL((step_many_kernel<W, C, NCH, 1, 12>), step_grid<W>(q.one.B), dim3(step_block<W>()), 0, s, q);
+      else
+        hipLaunchKernelGGL((step_many_kernel<W, C, NCH, 0, CR>), step_grid<W>(q.one.B), dim3(step_block<W>()), 0, s, q);
+    });
   }
 };
 template <typename W, int C>
 struct LaunchReset {
   static void run(const ResetParams& p, hipStream_t s) {
-    if (tet::board_packed((int)sizeof(W), p.R))
-      hipLaunchKernelGGL((reset_kernel<W, C, true>), grid_for(p.B), dim3(kBlock), 0, s, p);
-    else
-      hipLaunchKernelGGL((reset_kernel<W, C, false>), grid_for(p.B), dim3(kBlock), 0, s, p);
+    tet::kernel_variant<W>(p.R, [&](auto, auto, auto pack) {
+      hipLaunchKernelGGL((reset_kernel<W, C, decltype(pack)::value>), grid_for(p.B), dim3(kBlock), 0, s, p);
+    });
   }
 };
 template <typename W, int C>
 struct LaunchRefresh {
   static void run(const RefreshParams& p, hipStream_t s) {
-    if (tet::board_packed((int)sizeof(W), p.R))
-      hipLaunchKernelGGL((refresh_kernel<W, C, true>), grid_for(p.B), dim3(kBlock), 0, s, p);
-    else
-      hipLaunchKernelGGL((refresh_kernel<W, C, false>), grid_for(p.B), dim3(kBlock), 0, s, p);
+    tet::kernel_variant<W>(p.R, [&](auto, auto, auto pack) {
+      hipLaunchKernelGGL((refresh_kernel<W, C, decltype(pack)::value>), grid_for(p.B), dim3(kBlock), 0, s, p);
+    });
   }
 };
 template <typename W, int C>
 struct LaunchRollouts {
   static void run(const RolloutParams& p, hipStream_t s) {
-    if (packed_geometry<W>(p.R))
-      hipLaunchKernelGGL((rollouts_kernel<W, C, packed_chunks<W>()>), rollout_grid(p.B * p.a_max), dim3(kRolloutBlock), 0, s, p);
-    else
-      hipLaunchKernelGGL((rollouts_kernel<W, C, 0>), rollout_grid(p.B * p.a_max), dim3(kRolloutBlock), 0, s, p);
+    tet::kernel_variant<W>(p.R, [&](auto nch, auto, auto) {
+      hipLaunchKernelGGL((rollouts_kernel<W, C, decltype(nch)::value>), rollout_grid(p.B * p.a_max), dim3(kRolloutBlock), 0, s, p);
+    });
   }
 };
 template <typename W, int C>
 struct LaunchGreedy {
   static void run(const GreedyParams& p, hipStream_t s) {
-    if (packed_geometry<W>(p.R))
-      hipLaunchKernelGGL((greedy_kernel<W, C, packed_chunks<W>()>), grid_for(p.B), dim3(kBlock), 0, s, p);
-    else
-      hipLaunchKernelGGL((greedy_kernel<W, C, 0>), grid_for(p.B), dim3(kBlock), 0, s, p);
+    tet::kernel_variant<W>(p.R, [&](auto nch, auto, auto) {
+      hipLaunchKernelGGL((greedy_kernel<W, C, decltype(nch)::value>), grid_for(p.B), dim3(kBlock), 0, s, p);
+    });
   }
 };
 template <typename W, int C>
 struct LaunchAfter {
   static void run(const AfterParams& p, hipStream_t s) {
-    if (packed_geometry<W>(p.R))
-      hipLaunchKernelGGL((afterstates_kernel<W, C, packed_chunks<W>()>), grid_for(p.B), dim3(kBlock), 0, s, p);
-    else
-      hipLaunchKernelGGL((afterstates_kernel<W, C, 0>), grid_for(p.B), dim3(kBlock), 0, s, p);
+    tet::kernel_variant<W>(p.R, [&](auto nch, auto, auto) {
+      hipLaunchKernelGGL((afterstates_kernel<W, C, decltype(nch)::value>), grid_for(p.B), dim3(kBlock), 0, s, p);
+    });
   }
 };
 
@@ -1233,14 +1097,8 @@ static int fill_step_params(StepParams& p, const TetrisDesc* desc, void* cols, u
   p.step_counter = nullptr;
   p.seed = seed;
   p.step_rel = 0;
-  p.cfg.R = desc->num_rows;
-  p.cfg.n_pieces = desc->n_pieces;
-  p.cfg.auto_reset = auto_reset;
-  p.cfg.key_step = tet::hash_key(seed, step_idx * 4u + 0u);
-  p.cfg.key_policy = tet::hash_key(seed, step_idx * 4u + 3u);
-  p.cfg.compute_obs = obs != nullptr;
-  p.cfg.has_direct_by = desc->has_direct_by;
-  for (int i = 0; i < 8; ++i) p.cfg.direct_by[i] = desc->direct_by[i];
+  tet::fill_step_cfg(p.cfg, desc, auto_reset, obs != nullptr);
+  tet::step_keys(seed, step_idx, p.cfg);
   build_table(desc, &p.tab);
   return TETRIS_OK;
 }
@@ -1274,28 +1132,30 @@ int tetris_hip_step_call_init(void* call_, const TetrisDesc* desc, void* cols, u
   return TETRIS_OK;
 }
 
-int tetris_hip_step_call_run(void* call_, const int32_t* action, uint64_t step_idx, void* hip_stream) {
-  TetrisStepCall* call = static_cast<TetrisStepCall*>(call_);
+// what the three runs share: the checks, then this step's action / action_out and keys into the bound parameters
+static int step_call_begin(void* call_, const int32_t* action, uint64_t step_idx, TetrisStepCall*& call) {
+  call = static_cast<TetrisStepCall*>(call_);
   if (!call) return TETRIS_E_NULL;
   if (call->magic != kStepCallMagic) return TETRIS_E_DESC;
-  StepParams& p = call->p;
-  p.action = action;
-  p.action_out = action ? nullptr : call->action_out;
-  p.cfg.key_step = tet::hash_key(call->seed, step_idx * 4u + 0u);
-  p.cfg.key_policy = tet::hash_key(call->seed, step_idx * 4u + 3u);
-  return dispatch<LaunchStep>(&call->desc, p, (hipStream_t)hip_stream);
+  call->p.action = action;
+  call->p.action_out = action ? nullptr : call->action_out;
+  tet::step_keys(call->seed, step_idx, call->p.cfg);
+  return TETRIS_OK;
+}
+
+int tetris_hip_step_call_run(void* call_, const int32_t* action, uint64_t step_idx, void* hip_stream) {
+  TetrisStepCall* call;
+  const int rc = step_call_begin(call_, action, step_idx, call);
+  if (rc) return rc;
+  return dispatch<LaunchStep>(&call->desc, call->p, (hipStream_t)hip_stream);
 }
 
 int tetris_hip_step_call_run_gather(void* call_, const int32_t* action, uint64_t step_idx, uint64_t* done_bits,
                                     uint32_t* status_snapshot, void* hip_stream) {
-  TetrisStepCall* call = static_cast<TetrisStepCall*>(call_);
-  if (!call) return TETRIS_E_NULL;
-  if (call->magic != kStepCallMagic) return TETRIS_E_DESC;
+  TetrisStepCall* call;
+  const int rc = step_call_begin(call_, action, step_idx, call);
+  if (rc) return rc;
   StepParams p = call->p;  // (a copy: the bound call itself stays free of the payload pointers)
-  p.action = action;
-  p.action_out = action ? nullptr : call->action_out;
-  p.cfg.key_step = tet::hash_key(call->seed, step_idx * 4u + 0u);
-  p.cfg.key_policy = tet::hash_key(call->seed, step_idx * 4u + 3u);
   p.done_bits = reinterpret_cast<unsigned long long*>(done_bits);
   p.status_snapshot = status_snapshot;
   return dispatch<LaunchStep>(&call->desc, p, (hipStream_t)hip_stream);
@@ -1322,12 +1182,11 @@ const char* tetris_hip_source_hash(void) { return TET_SRC_HASH; }
 
 int tetris_hip_step_call_run_counted(void* call_, const int32_t* action, const uint64_t* step_counter, uint32_t step_rel,
                                      void* hip_stream) {
-  TetrisStepCall* call = static_cast<TetrisStepCall*>(call_);
-  if (!call || !step_counter) return TETRIS_E_NULL;
-  if (call->magic != kStepCallMagic) return TETRIS_E_DESC;
+  if (!step_counter) return TETRIS_E_NULL;
+  TetrisStepCall* call;
+  const int rc = step_call_begin(call_, action, 0, call);  // (the kernel derives the keys from the counter)
+  if (rc) return rc;
   StepParams p = call->p;  // (a copy: the bound call itself stays usable for plain runs)
-  p.action = action;
-  p.action_out = action ? nullptr : call->action_out;
   p.step_counter = step_counter;
   p.step_rel = step_rel;
   return dispatch<LaunchStep>(&call->desc, p, (hipStream_t)hip_stream);
