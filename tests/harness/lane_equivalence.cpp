@@ -1,9 +1,11 @@
 // lane_equivalence.cpp -- TEST HARNESS ONLY (tests/test_step_lane_equivalence.py compiles it with g++).
-// Holds a FROZEN copy of valid_mask and board_features (with the helpers they are made of and the table
-// fields valid_mask reads) as they stood before the step kernel's instruction-count work, renamed *_ref,
-// and compares them with the present tet::valid_mask (in the form env_step uses: TOP on 32-bit boards of
-// up to ten columns) and tet::board_features for <uint32_t, 10>.  The copies are never edited along with the
-// product: they are the yardstick.
+// Compares tet::valid_mask (the top-rows form env_step uses on 32-bit boards AND the general form refresh_kernel
+// keeps) and tet::board_features (12-row tables, and the packed 10-row form where R <= 20) with ONE yardstick
+// that is no form of them: plain loops over a board's cells, no tables and no bit-parallel words.  The valid
+// mask is worked out one placement at a time by the rule stated above valid_mask in tetris_core.hpp, the six
+// feature integers cell by cell as oracle/tetris_oracle.c states them.  The yardstick takes only the piece
+// geometry (tet::kCatalogue) and the mask layout (tet::mask_bit) from the product, and the test pins it to the
+// oracle: its masks to the terminal flags of the oracle's placements, its features to the oracle's.
 #include <stdint.h>
 #include <string.h>
 
@@ -11,229 +13,155 @@
 #include "../../tetris_amd/csrc/tetris_core.hpp"
 #include "../../tetris_amd/csrc/tetris_table.hpp"
 
-namespace tet {
-// ======================= frozen reference copies ==========================================================
-TET_HD constexpr int level_stride_ref(int C) { return C <= 10 ? 10 : 12; }
-inline void pack_mask_fields_ref(const CatOrient& o, OrientEntry* e, int C) {
-  const int LS = level_stride_ref(C);
-  int H = 0;
-  for (int j = 0; j < o.w; ++j)
-    if (o.b[j] + o.n[j] > H) H = o.b[j] + o.n[j];
-  for (int j = 0; j < o.w; ++j) e->sh[j] = (uint32_t)(LS * (H - o.b[j] - 1) + j);
-  for (int j = o.w; j < 4; ++j) e->sh[j] = e->sh[0];  // absent columns repeat column 0's term (OR is idempotent)
-  e->vert4 = (o.w == 1 && H == 4) ? ~0u : 0u;
-  for (int t = 1; t < 3; ++t) {  // board row R-3+t holds piece row rho when the anchor is R+1-H
-    const int rho = t - 4 + H;
-    e->rj0[t - 1] = 31;  // no such row: the interval is empty
-    e->rj1[t - 1] = 0;
-    if (rho < 0 || rho > H - 2) continue;
-    int j0 = -1, j1 = -1;
-    for (int j = 0; j < o.w; ++j)
-      if (o.b[j] <= rho && rho < o.b[j] + o.n[j]) {
-        if (j0 < 0) j0 = j;
-        j1 = j;
-      }
-    e->rj0[t - 1] = (uint32_t)j0;
-    e->rj1[t - 1] = (uint32_t)j1;
-  }
-}
-
-template <typename W, int C>
-TET_HD uint64_t valid_mask_ref(const W (&col)[C], const int (&h)[C], const OrientEntry* tab, uint64_t fullmask, int R) {
-  static_assert(C <= 12, "four 12-bit level fields + one empty field fill the 64-bit level word; 12-bit mask fields");
-  constexpr int LS = level_stride_ref(C);
-  typedef typename MissBits<C>::type FT;
-  uint32_t P[3] = {0u, 0u, 0u};
-#pragma unroll
-  for (int c = 0; c < C; ++c) P[c >> 2] |= (uint32_t)h[c] << (8 * (c & 3));
-  uint32_t lv[4];
-#pragma unroll
-  for (int l = 1; l <= 4; ++l) {
-    // byte b of P + K has bit 7 set iff h_b > R - l  (h <= 63, K <= 127: no carry between bytes)
-    const uint32_t K = (uint32_t)(127 - (R - l)) * 0x01010101u;
-    uint32_t g = 0;
-#pragma unroll
-    for (int q = 0; q < (C + 3) / 4; ++q)
-      g |= ((((P[q] + K) & 0x80808080u) * 0x00204081u) >> 28) << (4 * q);  // gather the four bit-7s
-    lv[l - 1] = g;
-  }
-  const uint64_t Z = ((uint64_t)lv[0] << LS) | ((uint64_t)lv[1] << (2 * LS)) | ((uint64_t)lv[2] << (3 * LS)) |
-                     ((uint64_t)lv[3] << (4 * LS));
-  // A placement that pokes above row R - 1 is rescued only by a row among R-3 .. R-1 that the piece
-  // completes, i.e. one that misses at most four cells.  A cell in row R-3 or above means h >= R - 2
-  // (level set 3), so when fewer than C - 4 columns reach that height no such row exists: the whole
-  // rescue evaluation (a third of this function) is skipped -- by the wavefront, when none of its
-  // envs needs it, which is the rule for boards that are not stacked to the top.
-  const bool rescue = !TET_RESCUE_SKIP || TET_WAVE_ANY(popc(lv[2]) >= C - 4);
-  uint32_t X[3] = {0u, 0u, 0u}, Y[3] = {0u, 0u, 0u};
-  uint32_t rv1 = 0, rv2 = 0;
-  if (rescue) {
-    FT Fall = 0;
-#pragma unroll
-    for (int c = 0; c < C; ++c) Fall |= (FT)((uint32_t)(col[c] >> (R - 3)) & 7u) << (3 * c);  // cells of rows R-3..R-1
-    const FT Mall = (FT)~Fall;  // missing cells, 3 bits per column
-    constexpr FT kEveryThird = (FT)0x9249249249249249ull & (FT)(((FT)1 << (3 * C)) - 1);  // bit 3c
-    constexpr FT kTop = (FT)1 << (8 * sizeof(FT) - 1);
-#pragma unroll
-    for (int t = 0; t < 3; ++t) {
-      const FT m = (FT)(Mall >> t) & kEveryThird;                     // bit 3c: column c misses row R-3+t
-      const int lo = (ctz_any((FT)(m | kTop)) * 11) >> 5;              // / 3
-      const int hi = ((bitlen((FT)(m | 1)) - 1) * 11) >> 5;            // (bitlen: the top bit of m is never set)
-      X[t] = ~0u << hi;
-      Y[t] = m ? (2u << lo) - 1u : 0u;  // a full row (only on boards that were set from outside) rescues nothing
-    }
-    const uint32_t s0 = X[0] & Y[0], s1 = X[1] & Y[1], s2 = X[2] & Y[2];
-    rv1 = s0 | s1 | s2;  // vertical Straight: any of its three lower rows
-    rv2 = s1 & s2;       //                    / both of R-2, R-1
-  }
-  const uint32_t cm = (1u << C) - 1u;
-  uint64_t mask = 0;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const OrientEntry& e = tab[k];
-    uint32_t r = 0;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) r |= (uint32_t)(Z >> e.sh[j]);
-    const uint32_t i1 = r >> LS, i2 = r;
-    uint32_t v = ~i1;
-    if (rescue) {
-      // rescue by one cleared row (e = 1)
-      uint32_t r1 = ((X[1] >> e.rj1[0]) & (Y[1] >> e.rj0[0])) | ((X[2] >> e.rj1[1]) & (Y[2] >> e.rj0[1]));
-      r1 = (rv1 & e.vert4) | (r1 & ~e.vert4);
-      const uint32_t r2 = rv2 & e.vert4;
-      v |= ~(i2 & ~r2) & r1;
-    }
-    mask |= (uint64_t)(v & cm) << (kFieldStride * k);
-  }
-  return mask & fullmask;
-}
-
-template <typename W, int NCH = 0, int CR = 12>
-TET_HD void col_own_ref(W x, int hi, int R, const uint8_t* lut, W& ho, int& nh, int& f1, int& f7) {
-  ho = (W)(~x & lowmask<W>(hi));                   // holes (state.py:210-213)
-  nh = popc(ho);
-  const uint8_t* lut_a = lut + LutLayout<CR>::kHoleA;
-  const uint8_t* lut_u = lut + LutLayout<CR>::kHoleU;
-  int d7 = 0, u = 0;
-  if (!(TET_ABLATE & 16)) {
-#pragma unroll
-    for (int k = 0; CR * k < (int)(8 * sizeof(W)) - 1; ++k) {
-      // rows beyond the stored ones are zero: entry 0 adds nothing, so extra chunks are harmless
-      if (NCH > 0 ? k < NCH : (k < 2 || CR * k < R + 4)) {
-        const uint32_t up = (uint32_t)(x >> (CR * k));
-        const uint32_t idx = (NCH > 0 && k == NCH - 1) ? up : (up & (uint32_t)(LutLayout<CR>::kHoleEntries - 1));
-        const int uk = lut_u[idx];
-        u += uk;
-        d7 += lut_a[idx];
-        const bool more = NCH > 0 ? k + 1 < NCH : (CR * (k + 1) < R + 4);  // rows above this chunk exist
-        if (CR * (k + 1) < (int)(8 * sizeof(W)) && more) d7 += uk * popc((W)(x >> (CR * (k + 1))));
-      }
-    }
-  }
-  f1 = 2 * u;
-  f7 = d7;
-}
-
-// Row transitions of one column against its LEFT neighbour (state.py:203-204,223-226,
-// 246-248,253-254).  Empty column: the filled cells of the left neighbour = hL - its holes
-// (:254); otherwise max(hL-h, 0).
-template <typename W>
-TET_HD int col_rowtrans_ref(W x, W L, int hi, int hL, int nh_left) {
-  const int dl = hL - hi;
-  return popc((W)((x ^ L) & lowmask<W>(hi))) + (dl > 0 ? dl : 0) - ((hi == 0) ? nh_left : 0);
-}
-
-// Cumulative wells of one column (state.py:223-233 inside the column, :258-272 above it).
-// A well cell is an empty cell whose two neighbours are filled: inside the column (rows < h) the
-// walls count as filled on every stored row (state.py:177-178); above it only rows below
-// min(hL, hR) count, with wall height R (state.py:179,258-261) -- neighbours have no cells at or
-// above their own height, so for inner columns the set is simply ~x & L & R, and for the edge
-// columns the wall side is cut at max(h, R).  Every maximal vertical run of k well cells adds
-// k(k+1)/2: summed per 12-row chunk through the wells tables (S, lead, trail) with a carry for
-// runs that cross chunk borders -- no data-dependent loop.  (A full chunk has trail = lead = 12.)
-template <typename W, int NCH = 0, int CR = 12>
-TET_HD int col_wells_ref(W x, W L, W Rr, int hi, int R, bool left_wall, bool right_wall, const uint8_t* lut) {
-  W w = (W)(~x & L & Rr);
-  if (left_wall || right_wall) w = (W)(w & lowmask<W>(hi > R ? hi : R));
-  const uint8_t* lut_s = lut + LutLayout<CR>::kWellsS;
-  const uint8_t* lut_lead = lut + LutLayout<CR>::kWellsLead;
-  const uint8_t* lut_trail = lut + LutLayout<CR>::kWellsTrail;
-  int total = 0, carry = 0;
-#pragma unroll
-  for (int k = 0; CR * k < (int)(8 * sizeof(W)) - 1; ++k) {
-    if (NCH > 0 ? k < NCH : (k < 2 || CR * k < R + 4)) {  // rows beyond the stored ones hold no well cells
-      const uint32_t up = (uint32_t)(w >> (CR * k));
-      const uint32_t idx = (NCH > 0 && k == NCH - 1) ? up : (up & (uint32_t)(LutLayout<CR>::kWellsEntries - 1));
-      const bool last = NCH > 0 && k == NCH - 1;
-      total += lut_s[idx];
-      if (k == 0) {
-        if (!last) carry = lut_trail[idx];
-      } else {
-        const int lead = lut_lead[idx];
-        total += carry * lead;
-        if (!last) {
-          const int trail = lut_trail[idx];  // read unconditionally: a select, not a branch around the load
-          carry = (lead == CR) ? carry + CR : trail;
-        }
-      }
-    }
-  }
-  return (TET_ABLATE & 32) ? 0 : total;
-}
-// state.py:175-280.  out = f0,f1,f2,f4,f5,f7.
-// PACKW: hole_lut is an AfterLut (packed wells entries) instead of a LutLayout<CR>
-template <typename W, int C, int NCH = 0, int CR = 12, bool PACKW = false>
-TET_HD void board_features_ref(const W (&col)[C], const int (&h)[C], int R, const uint8_t* hole_lut,
-                           int& rows_with_holes, int& col_trans, int& holes, int& wells, int& row_trans,
-                           int& hole_depth) {
-  const W wall = lowmask<W>(R + 4);  // walls of ones over every stored row (state.py:177-178)
-  W hole_rows = 0;
-  int f1 = C;                      // one unconditional transition per column (state.py:194)
-  int f2 = 0, f4 = 0, f7 = 0;
-  int f5 = R - popc(col[C - 1]);   // state.py:190
-  int nh_left = 0;                 // holes of the left neighbour (the wall has none)
-#pragma unroll
-  for (int i = 0; i < C; ++i) {
-    const W L = (i == 0) ? wall : col[i - 1];
-    const W Rr = (i == C - 1) ? wall : col[i + 1];
-    const int hL = (i == 0) ? R : h[i - 1];       // state.py:179 wall height = num_rows
-    W ho;
-    int nh, d1, d7;
-    col_own_ref<W, NCH, CR>(col[i], h[i], R, hole_lut, ho, nh, d1, d7);
-    f1 += d1;
-    f2 += nh;
-    f7 += d7;
-    hole_rows |= ho;                              // state.py:215
-    f5 += col_rowtrans_ref<W>(col[i], L, h[i], hL, nh_left);
-    nh_left = nh;
-    if (PACKW)
-      f4 += col_wells_packed<W, NCH>(col[i], L, Rr, h[i], R, i == 0, i == C - 1,
-                                     reinterpret_cast<const uint32_t*>(hole_lut + AfterLut::kWellsPack));
-    else
-      f4 += col_wells_ref<W, NCH, CR>(col[i], L, Rr, h[i], R, i == 0, i == C - 1, hole_lut);
-    if (TET_FENCE_EVERY > 0 && i % TET_FENCE_EVERY == TET_FENCE_EVERY - 1 && i + 1 < C) {
-      TET_PIN(f1);
-      TET_PIN(f2);
-      TET_PIN(f4);
-      TET_PIN(f5);
-      TET_PIN(f7);
-      TET_SCHED_FENCE();
-    }
-  }
-  rows_with_holes = popc(hole_rows);  // state.py:274-275
-  col_trans = f1;
-  holes = f2;
-  wells = f4;
-  row_trans = f5;
-  hole_depth = f7;
-}
-// ======================= end of the frozen copies =========================================================
-}  // namespace tet
-
 namespace {
 
-constexpr int C = 10;
 typedef uint32_t W;
+constexpr int kMaxStoredRows = 32;  // R + 4 stored rows of a 32-bit board
+
+// ======================= the yardstick: cells, loops, no tables ===========================================
+// A board as the yardstick sees it, with its walls: columns -1 and C, filled on every stored row.  The boards
+// it is given hold no cell at or above row R (the callers count the others as dirty and leave them out).
+template <int C>
+struct Cells {
+  int8_t cell[kMaxStoredRows][C + 2];  // cell[r][c + 1] = cell (r, c), row 0 = bottom; [0] and [C + 1] the walls
+  int h[C];                            // lowest free row of each column
+  int filled[kMaxStoredRows];          // cells in each row, walls left out
+};
+
+template <int C>
+void cells_of(const W (&col)[C], int R, Cells<C>* b) {
+  for (int r = 0; r < R + 4; ++r) {
+    b->cell[r][0] = b->cell[r][C + 1] = 1;
+    b->filled[r] = 0;
+    for (int c = 0; c < C; ++c) {
+      b->cell[r][c + 1] = (int8_t)((col[c] >> r) & 1u);
+      b->filled[r] += b->cell[r][c + 1];
+    }
+  }
+  for (int c = 0; c < C; ++c) {
+    b->h[c] = R + 4;
+    while (b->h[c] > 0 && !b->cell[b->h[c] - 1][c + 1]) --b->h[c];
+  }
+}
+
+// What a placement needs of one orientation: its width, its height H = max_j (b_j + n_j), the bottom offsets
+// b_j of its columns and the number of its cells in each of its rows.  Read once from the catalogue.
+struct Shape {
+  int w, H, b[4], in_row[4];
+};
+struct Shapes {
+  Shape of[TETRIS_N_CATALOGUE][4];  // [piece][k = 2L + o]; w = 0: no such orientation
+  Shapes() {
+    memset(of, 0, sizeof(of));
+    for (int p = 0; p < TETRIS_N_CATALOGUE; ++p)
+      for (int l = 0; l < 2; ++l)
+        for (int oi = 0; oi < tet::kCatalogue[p].n_orient[l]; ++oi) {
+          const tet::CatOrient& o = tet::kCatalogue[p].o[l][oi];
+          Shape& s = of[p][2 * l + oi];
+          s.w = o.w;
+          for (int j = 0; j < o.w; ++j) {
+            s.b[j] = o.b[j];
+            if (o.b[j] + o.n[j] > s.H) s.H = o.b[j] + o.n[j];
+            for (int k = o.b[j]; k < o.b[j] + o.n[j]; ++k) ++s.in_row[k];
+          }
+        }
+  }
+};
+const Shapes kShapes;
+
+// One placement: shape s with its left column at c.  The piece lands at a = max_j (h[c+j] - b_j), so its cells
+// fall on free cells; the rows a .. a+H-1 that are full with them are removed and the rows above drop; the
+// placement is terminal iff a cell remains at row >= R.  The stack holds no cell there and rows only move down,
+// so only the piece's own rows can: each is visited bottom up with the number of rows removed below it.
+// *rescued: the piece poked above row R - 1 before the clear and the placement is not terminal after it.
+template <int C>
+inline bool placement_survives(const Cells<C>& b, const Shape& s, int c, int R, bool* rescued) {
+  int a = 0;
+  for (int j = 0; j < s.w; ++j)
+    if (b.h[c + j] - s.b[j] > a) a = b.h[c + j] - s.b[j];
+  int removed = 0;
+  bool terminal = false;
+  for (int k = 0; k < s.H; ++k) {
+    const bool full = b.filled[a + k] + s.in_row[k] == C;
+    removed += full;
+    terminal |= !full & (a + k - removed >= R);  // a row of the piece that stays: it holds a cell
+  }
+  *rescued = a + s.H > R && !terminal;
+  return !terminal;
+}
+
+// bit mask_bit(2L + o, c) is set iff the placement exists (the orientation does, and c + w <= C) and is not terminal
+template <int C>
+uint64_t yardstick_mask(const Cells<C>& b, int piece, int R, int64_t* n_rescued) {
+  uint64_t mask = 0;
+  for (int k = 0; k < 4; ++k) {
+    const Shape& s = kShapes.of[piece][k];
+    if (s.w == 0) continue;
+    for (int c = 0; c + s.w <= C; ++c) {
+      bool rescued;
+      mask |= (uint64_t)placement_survives<C>(b, s, c, R, &rescued) << tet::mask_bit(k, c);
+      *n_rescued += rescued;
+    }
+  }
+  return mask;
+}
+
+// The six feature integers, cell by cell, as oracle/tetris_oracle.c states them (rows with holes, column
+// transitions, holes, cumulative wells, row transitions, hole depth).  The walls are R high.
+//  * a hole is a free cell below its column's top; its depth counts, when the cell on top of it is filled, the
+//    filled cells of the column above it;
+//  * column transitions: changes of filled / free along a column from the floor (filled) to its top, and one
+//    more for the free cell above the top (an empty column has that one alone);
+//  * row transitions: below a column's top, every cell that differs from its left neighbour, and the rows by
+//    which the left neighbour is higher; an empty column counts its left neighbour's filled cells instead; the
+//    right wall counts R less the filled cells of the last column;
+//  * a well cell is a free cell with both neighbours filled, below the column's top or, above it, below the
+//    lower of the neighbours' tops; every well cell adds the length of the unbroken run of well cells that ends
+//    in it (a run of n adds n(n+1)/2).
+template <int C>
+void yardstick_features(const Cells<C>& b, int R, int (&f)[6]) {
+  auto at = [&](int r, int c) { return (int)b.cell[r][c + 1]; };
+  auto top = [&](int c) { return (c < 0 || c >= C) ? R : b.h[c]; };
+  bool row_has_hole[kMaxStoredRows] = {false};
+  int col_trans = 0, holes = 0, wells = 0, row_trans = 0, hole_depth = 0;
+  for (int c = 0; c < C; ++c) {
+    const int h = top(c), hl = top(c - 1), hr = top(c + 1);
+    int above = 0;  // filled cells of the column above the row in hand
+    for (int r = 0; r < h; ++r) above += at(r, c);
+    int run = 0;    // well cells in an unbroken run up to the row in hand
+    col_trans += 1;
+    for (int r = 0; r < h; ++r) {  // (sums of 0 / 1 terms: the cells are random, branches on them cost more)
+      const int cell = at(r, c), hole = 1 - cell;
+      const int well = hole & at(r, c - 1) & at(r, c + 1);
+      col_trans += cell != (r > 0 ? at(r - 1, c) : 1);
+      row_trans += cell != at(r, c - 1);
+      above -= cell;
+      holes += hole;
+      row_has_hole[r] |= (bool)hole;
+      hole_depth += hole * at(r + 1, c) * above;
+      run = well * (run + 1);
+      wells += run;
+    }
+    if (h > 0)
+      row_trans += hl > h ? hl - h : 0;
+    else
+      for (int r = 0; r < hl; ++r) row_trans += at(r, c - 1);
+    for (int r = h; r < hl && r < hr; ++r) {
+      run = (at(r, c - 1) & at(r, c + 1)) * (run + 1);
+      wells += run;
+    }
+  }
+  row_trans += R;
+  for (int r = 0; r < R + 4; ++r) row_trans -= at(r, C - 1);
+  f[0] = 0;
+  for (int r = 0; r < R + 4; ++r) f[0] += row_has_hole[r];
+  f[1] = col_trans;
+  f[2] = holes;
+  f[3] = wells;
+  f[4] = row_trans;
+  f[5] = hole_depth;
+}
+// ======================= end of the yardstick =============================================================
 
 struct alignas(16) Lut12 { uint8_t bytes[tet::kFeatureLutBytes]; };
 const Lut12 kLut12 = {{
@@ -244,25 +172,48 @@ const Lut10 kLut10 = {{
 #include "../../tetris_amd/csrc/tetris_feature_lut10.inc"
 }};
 
-struct Tables {
-  tet::SetTable now, ref;
-  int n_pieces;
-};
-
-void make_tables(int n_pieces, const int32_t* piece_ids, Tables* t) {
+void make_table(int C, int n_pieces, const int32_t* piece_ids, tet::SetTable* t) {
   TetrisDesc d;
   memset(&d, 0, sizeof(d));
   d.num_columns = C;
   d.n_pieces = n_pieces;
   for (int i = 0; i < n_pieces; ++i) d.piece_ids[i] = piece_ids[i];
-  tet::build_table(&d, &t->now);
-  t->ref = t->now;
-  for (int i = 0; i < n_pieces; ++i) {  // the reference's own shift / rescue fields
-    const tet::CatPiece& p = tet::kCatalogue[piece_ids[i]];
-    for (int l = 0; l < 2; ++l)
-      for (int oi = 0; oi < p.n_orient[l]; ++oi) tet::pack_mask_fields_ref(p.o[l][oi], &t->ref.orient[i][l * 2 + oi], C);
+  tet::build_table(&d, t);
+}
+
+struct Tally {
+  int64_t mask_bad = 0, feat_bad = 0, masks = 0;
+  int64_t rescued[16] = {0};
+  void add(const Tally& o) {
+    mask_bad += o.mask_bad;
+    feat_bad += o.feat_bad;
+    masks += o.masks;
+    for (int i = 0; i < 16; ++i) rescued[i] += o.rescued[i];
   }
-  t->n_pieces = n_pieces;
+};
+#pragma omp declare reduction(+ : Tally : omp_out.add(omp_in))
+
+// One clean board: valid_mask of every piece of the set in both present forms, and board_features in the table
+// variants the kernels instantiate for R, against the yardstick.
+template <int C>
+void check_board(const W (&col)[C], const Cells<C>& b, int R, const tet::SetTable& tab, int n_pieces,
+                 const int32_t* piece_ids, Tally* t) {
+  int h[C];
+  tet::heights_of<W, C>(col, h);
+  for (int i = 0; i < n_pieces; ++i) {
+    const uint64_t want = yardstick_mask<C>(b, piece_ids[i], R, &t->rescued[i]);
+    t->mask_bad += tet::valid_mask<W, C, true>(col, h, tab.orient[i], tab.fullmask[i], R) != want;
+    t->mask_bad += tet::valid_mask<W, C, false>(col, h, tab.orient[i], tab.fullmask[i], R) != want;
+    ++t->masks;
+  }
+  int f[6], g[6];
+  yardstick_features<C>(b, R, g);
+  tet::board_features<W, C, 0, 12>(col, h, R, kLut12.bytes, f[0], f[1], f[2], f[3], f[4], f[5]);
+  t->feat_bad += memcmp(f, g, sizeof(f)) != 0;
+  if (R <= 20) {  // the 10-row-chunk tables of the stepping kernels (board_features_u32_2x10)
+    tet::board_features<W, C, 2, 10>(col, h, R, kLut10.bytes, f[0], f[1], f[2], f[3], f[4], f[5]);
+    t->feat_bad += memcmp(f, g, sizeof(f)) != 0;
+  }
 }
 
 inline uint64_t mix64(uint64_t x) {
@@ -272,128 +223,144 @@ inline uint64_t mix64(uint64_t x) {
   return x ^ (x >> 31);
 }
 
-// valid placements of `mask` whose piece pokes above row R - 1 before the clear (they are valid only through
-// the rescue by a cleared row): anchor a = max_j (h[c+j] - b_j), a + H > R.  Independent of both forms.
-int count_rescued(uint64_t mask, const tet::CatPiece& p, const int (&h)[C], int R) {
-  int n = 0;
-  for (int l = 0; l < 2; ++l)
-    for (int oi = 0; oi < p.n_orient[l]; ++oi) {
-      const tet::CatOrient& o = p.o[l][oi];
-      int H = 0;
-      for (int j = 0; j < o.w; ++j)
-        if (o.b[j] + o.n[j] > H) H = o.b[j] + o.n[j];
-      for (int c = 0; c + o.w <= C; ++c) {
-        if (!((mask >> tet::mask_bit(2 * l + oi, c)) & 1)) continue;
-        int a = 0;
-        for (int j = 0; j < o.w; ++j)
-          if (h[c + j] - o.b[j] > a) a = h[c + j] - o.b[j];
-        if (a + H > R) ++n;
-      }
+// Set (i): rows R-4 .. R-1 of a 6-column window run through patterns (every `every`-th of the 2^24, offset by a
+// hash so that no bit is fixed), the window at every position 0 .. C-6; the other columns' top rows and every
+// row below R-4 are random (fixed seed); no cell at or above R.
+inline uint32_t window_pattern(uint64_t seed, int every, int64_t q) {
+  return (uint32_t)(q * every + (int64_t)(mix64(seed ^ (uint64_t)q) % (uint64_t)every));
+}
+
+template <int C>
+void window_board(int R, uint64_t seed, uint32_t pat, int pos, W (&col)[C]) {
+  const uint64_t r0 = mix64(seed * 31 + (uint64_t)pat * 8 + (uint64_t)pos);
+  for (int c = 0; c < C; ++c) {
+    const uint64_t rc = mix64(r0 + (uint64_t)c);
+    // below R-4: random cells, thinned or thickened by a per-column choice so that rows are sometimes near full
+    W low = (W)rc;
+    if ((rc >> 40) & 1) low |= (W)(rc >> 8);
+    if ((rc >> 41) & 1) low |= (W)(rc >> 16);
+    low &= tet::lowmask<W>(R - 4);
+    W top = (c >= pos && c < pos + 6) ? (W)((pat >> (4 * (c - pos))) & 15u) : (W)((rc >> 44) & 15u);
+    if (!(c >= pos && c < pos + 6) && ((rc >> 48) & 3) != 0) top = 15u >> ((rc >> 50) & 1);  // mostly stacked: rescues need it
+    col[c] = (W)(low | (top << (R - 4)));
+  }
+}
+
+template <int C>
+int64_t window_run(int R, int n_pieces, const int32_t* piece_ids, uint64_t seed, int every, int64_t* rescued,
+                   int64_t* checked, int64_t* feat_bad) {
+  tet::SetTable tab;
+  make_table(C, n_pieces, piece_ids, &tab);
+  Tally t;
+  const int64_t n_pat = ((int64_t)1 << 24) / every;
+#pragma omp parallel for schedule(static) reduction(+ : t)
+  for (int64_t q = 0; q < n_pat; ++q) {
+    const uint32_t pat = window_pattern(seed, every, q);
+    for (int pos = 0; pos + 6 <= C; ++pos) {
+      W col[C];
+      Cells<C> b;
+      window_board<C>(R, seed, pat, pos, col);
+      cells_of<C>(col, R, &b);
+      check_board<C>(col, b, R, tab, n_pieces, piece_ids, &t);
     }
-  return n;
+  }
+  for (int i = 0; i < n_pieces; ++i) rescued[i] += t.rescued[i];
+  *checked += t.masks;
+  *feat_bad += t.feat_bad;
+  return t.mask_bad;
 }
 
 }  // namespace
 
 extern "C" {
 
-// Set (i): rows R-4 .. R-1 of a 6-column window run through patterns (every `every`-th of the 2^24, offset by a
-// hash so that no bit is fixed), the window at every position 0 .. C-6; the other columns' top rows and every
-// row below R-4 are random (fixed seed); no cell at or above R.  Every piece of the set, full 48-bit mask.
-// Returns the number of mismatches; rescued[i] += rescued placements seen for piece i; *checked += masks compared.
-int64_t lane_vm_window(int R, int n_pieces, const int32_t* piece_ids, uint64_t seed, int every, int64_t* rescued,
-                       int64_t* checked) {
-  Tables t;
-  make_tables(n_pieces, piece_ids, &t);
-  int64_t bad = 0, n_chk = 0;
-  int64_t resc[16] = {0};
-  const int64_t n_pat = ((int64_t)1 << 24) / every;
-#pragma omp parallel for schedule(static) reduction(+ : bad, n_chk) reduction(+ : resc[:16])
-  for (int64_t q = 0; q < n_pat; ++q) {
-    const uint32_t pat = (uint32_t)(q * every + (int64_t)(mix64(seed ^ (uint64_t)q) % (uint64_t)every));
-    for (int pos = 0; pos + 6 <= C; ++pos) {
-      const uint64_t r0 = mix64(seed * 31 + (uint64_t)pat * 8 + (uint64_t)pos);
-      W col[C];
-      int h[C];
-      for (int c = 0; c < C; ++c) {
-        const uint64_t rc = mix64(r0 + (uint64_t)c);
-        // below R-4: random cells, thinned or thickened by a per-column choice so that rows are sometimes near full
-        W low = (W)rc;
-        if ((rc >> 40) & 1) low |= (W)(rc >> 8);
-        if ((rc >> 41) & 1) low |= (W)(rc >> 16);
-        low &= tet::lowmask<W>(R - 4);
-        W top = (c >= pos && c < pos + 6) ? (W)((pat >> (4 * (c - pos))) & 15u) : (W)((rc >> 44) & 15u);
-        if (!(c >= pos && c < pos + 6) && ((rc >> 48) & 3) != 0) top = 15u >> ((rc >> 50) & 1);  // mostly stacked: rescues need it
-        col[c] = (W)(low | (top << (R - 4)));
-      }
-      tet::heights_of<W, C>(col, h);
-      for (int i = 0; i < n_pieces; ++i) {
-        const uint64_t a = tet::valid_mask<W, C, true>(col, h, t.now.orient[i], t.now.fullmask[i], R);
-        const uint64_t b = tet::valid_mask_ref<W, C>(col, h, t.ref.orient[i], t.ref.fullmask[i], R);
-        bad += (a != b);
-        ++n_chk;
-        resc[i] += count_rescued(b, tet::kCatalogue[piece_ids[i]], h, R);
-      }
-    }
-  }
-  for (int i = 0; i < n_pieces; ++i) rescued[i] += resc[i];
-  *checked += n_chk;
-  return bad;
+// Set (i) on C = 8 or 10 columns, every piece of the set.  Returns the number of mask mismatches (-1: C not built);
+// rescued[i] += rescued placements seen for piece i; *checked += masks compared; *feat_bad += feature mismatches.
+int64_t lane_vm_window(int C, int R, int n_pieces, const int32_t* piece_ids, uint64_t seed, int every,
+                       int64_t* rescued, int64_t* checked, int64_t* feat_bad) {
+  if (C == 8) return window_run<8>(R, n_pieces, piece_ids, seed, every, rescued, checked, feat_bad);
+  if (C == 10) return window_run<10>(R, n_pieces, piece_ids, seed, every, rescued, checked, feat_bad);
+  return -1;
 }
 
-// Sets (ii), (iii): given boards (ten column words each).  valid_mask for every piece of the set in both of the
-// present forms (TOP as env_step calls it, and the general one refresh_kernel keeps) against the reference, and
-// board_features in the table variants the kernels instantiate for R.  out[0] += mask mismatches, out[1] +=
-// feature mismatches, out[2] += boards with a cell at or above R (the caller asserts 0), out[3] += masks compared,
+// The boards of set (i) themselves (ten columns): cols[(q * 5 + pos) * 10 + c], (2^24 / every) * 5 boards.
+void lane_window_cols(int R, uint64_t seed, int every, uint32_t* cols) {
+  const int64_t n_pat = ((int64_t)1 << 24) / every;
+  for (int64_t q = 0; q < n_pat; ++q)
+    for (int pos = 0; pos < 5; ++pos) {
+      W col[10];
+      window_board<10>(R, seed, window_pattern(seed, every, q), pos, col);
+      memcpy(cols + (q * 5 + pos) * 10, col, sizeof(col));
+    }
+}
+
+// Sets (ii), (iii): given boards (ten column words each).  out[0] += mask mismatches, out[1] += feature
+// mismatches, out[2] += boards with a cell at or above R (the caller asserts 0), out[3] += masks compared,
 // out[4] += wavefronts (64 consecutive boards) whose rescue evaluation runs, out[5] += wavefronts.
 void lane_boards(int R, int n_pieces, const int32_t* piece_ids, const uint32_t* cols, int64_t n, int64_t* out) {
-  Tables t;
-  make_tables(n_pieces, piece_ids, &t);
-  int64_t bad_m = 0, bad_f = 0, dirty = 0, n_chk = 0, wav_run = 0, wav = 0;
-#pragma omp parallel for schedule(static) reduction(+ : bad_m, bad_f, dirty, n_chk, wav_run, wav)
+  constexpr int C = 10;
+  tet::SetTable tab;
+  make_table(C, n_pieces, piece_ids, &tab);
+  Tally t;
+  int64_t dirty = 0, wav_run = 0, wav = 0;
+#pragma omp parallel for schedule(static) reduction(+ : t, dirty, wav_run, wav)
   for (int64_t w0 = 0; w0 < n; w0 += 64) {
     bool any = false;
-    for (int64_t b = w0; b < w0 + 64 && b < n; ++b) {
+    for (int64_t i = w0; i < w0 + 64 && i < n; ++i) {
       W col[C];
-      int h[C];
-      for (int c = 0; c < C; ++c) col[c] = cols[b * C + c];
-      tet::heights_of<W, C>(col, h);
+      Cells<C> b;
       bool over = false;
-      int n3 = 0;
       for (int c = 0; c < C; ++c) {
+        col[c] = cols[i * C + c];
         over |= (col[c] >> R) != 0;
-        n3 += h[c] >= R - 2;
       }
       if (over) {
         ++dirty;
         continue;
       }
+      cells_of<C>(col, R, &b);
+      int n3 = 0;
+      for (int c = 0; c < C; ++c) n3 += b.h[c] >= R - 2;
       any |= n3 >= C - 4;
-      for (int i = 0; i < n_pieces; ++i) {
-        const uint64_t r = tet::valid_mask_ref<W, C>(col, h, t.ref.orient[i], t.ref.fullmask[i], R);
-        bad_m += tet::valid_mask<W, C, true>(col, h, t.now.orient[i], t.now.fullmask[i], R) != r;
-        bad_m += tet::valid_mask<W, C, false>(col, h, t.now.orient[i], t.now.fullmask[i], R) != r;
-        ++n_chk;
-      }
-      int f[6], g[6];
-      tet::board_features<W, C, 0, 12>(col, h, R, kLut12.bytes, f[0], f[1], f[2], f[3], f[4], f[5]);
-      tet::board_features_ref<W, C, 0, 12>(col, h, R, kLut12.bytes, g[0], g[1], g[2], g[3], g[4], g[5]);
-      bad_f += memcmp(f, g, sizeof(f)) != 0;
-      if (R <= 20) {  // the 10-row-chunk tables of the stepping kernels
-        tet::board_features<W, C, 2, 10>(col, h, R, kLut10.bytes, f[0], f[1], f[2], f[3], f[4], f[5]);
-        tet::board_features_ref<W, C, 2, 10>(col, h, R, kLut10.bytes, g[0], g[1], g[2], g[3], g[4], g[5]);
-        bad_f += memcmp(f, g, sizeof(f)) != 0;
-      }
+      check_board<C>(col, b, R, tab, n_pieces, piece_ids, &t);
     }
     ++wav;
     wav_run += any;
   }
-  out[0] += bad_m;
-  out[1] += bad_f;
+  out[0] += t.mask_bad;
+  out[1] += t.feat_bad;
   out[2] += dirty;
-  out[3] += n_chk;
+  out[3] += t.masks;
   out[4] += wav_run;
   out[5] += wav;
+}
+
+// The yardstick alone, for the test that pins it to the oracle, on clean boards (ten column words each):
+// masks[i] = its valid mask of catalogue piece `pid` on board i.
+void lane_yardstick_masks(int R, int pid, const uint32_t* cols, int64_t n, uint64_t* masks) {
+  constexpr int C = 10;
+  for (int64_t i = 0; i < n; ++i) {
+    W col[C];
+    Cells<C> b;
+    int64_t rescued = 0;
+    memcpy(col, cols + i * C, sizeof(col));
+    cells_of<C>(col, R, &b);
+    masks[i] = yardstick_mask<C>(b, pid, R, &rescued);
+  }
+}
+
+// feats[6 i ..] = its six feature integers of board i
+void lane_yardstick_features(int R, const uint32_t* cols, int64_t n, int32_t* feats) {
+  constexpr int C = 10;
+  for (int64_t i = 0; i < n; ++i) {
+    W col[C];
+    Cells<C> b;
+    int f[6];
+    memcpy(col, cols + i * C, sizeof(col));
+    cells_of<C>(col, R, &b);
+    yardstick_features<C>(b, R, f);
+    for (int q = 0; q < 6; ++q) feats[6 * i + q] = f[q];
+  }
 }
 
 }  // extern "C"

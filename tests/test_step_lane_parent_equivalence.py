@@ -1,132 +1,25 @@
-"""The step kernel's lane logic against a frozen copy of its PARENT form, on the CPU.
-
-`tests/harness/lane_parent_equivalence.cpp` holds `valid_mask` (top-rows and general form) and `board_features`
-(with `col_own`, `col_rowtrans`, `col_wells`) for `<uint32_t, 10>` as they stood before the second round of
-instruction-count work on the step kernel (renamed `*_parent`) and compares them with the present ones:
-`valid_mask` in the top-rows form `env_step` uses (orientation loop bounded by the set's widest piece) AND in
-the general form, `board_features` in the 12-row form and in the 10-row form the step kernel runs (packed
-heights, no per-column height differences).  `test_step_lane_equivalence.py` keeps the older yardstick.  The inputs:
-
- (i)   boards whose rows R-4 .. R-1 run through every pattern of a 6-column window (2^24 patterns), the window
-       at each of its five positions, the other columns and the rows below randomised with a fixed seed, no cell
-       at or above R.  This is the set that forces the rescue by a cleared row, taken and skipped, for every
-       orientation; the test asserts that every piece met rescued placements.
- (ii)  boards sampled from oracle games at steady state (random play, fixed seed, after 256 steps).
- (iii) the boards of tests/golden g1 (10x20) and g4 that hold no cell at or above R.
-
-Every piece of the default set and of the nine-piece catalogue; the full 48-bit mask; all six feature integers;
-zero mismatches, no board of (i) or (ii) left out.  The features are compared on every board of (i) too.
-
-The harness also counts, without asserting on it, the wavefronts of (ii) in which a sharper rescue test (a row among
-R-3 .. R-1 whose missing cells span at most four adjacent columns) would still run the rescue evaluation: 28,909 of
-31,250 at R = 20 against 31,247 for the test that is built, so the sharper test was not built.  R = 20, and R = 10 and R = 24 (the extremes the 10-row-chunk
-tables and 32-bit boards serve).
-
-What was cut to stay under two minutes on 16 threads: (i) runs all 2^24 patterns x 5 positions for R = 20 with
-the nine-piece catalogue (the default set's two pieces are members of it and are run on every 16th pattern as a
-set of their own); R = 10 and R = 24 run every 16th pattern (the offset inside each block of 16 is hashed, so no
-pattern bit is fixed).  (ii) is 2,000,000 boards at R = 20 and 250,000 each at R = 10 and R = 24.
-"""
-import ctypes
-import os
-import subprocess
-
-import numpy as np
+"""The second seed of sets (i) and (ii) of the lane tests.  Everything is in tests/test_step_lane_equivalence.py:
+one harness, one plain yardstick, the input sets and the assertions; this file only calls it.  It holds no parent
+form of anything.  It keeps its name because its test ids are part of the suite's record."""
 import pytest
 
-from oracle import oracle as orc
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, "harness", "lane_parent_equivalence.cpp")
-NTHREADS = min(16, os.cpu_count() or 1)
-CATALOGUE9 = list(range(9))
-DEFAULT = [orc.CATALOGUE.index(n) for n in orc.PIECE_SETS["default"]]
-SETS = {"default": DEFAULT, "catalogue9": CATALOGUE9}
+import test_step_lane_equivalence as lane_tests
+from test_step_lane_equivalence import lane  # noqa: F401  (the fixture; the harness is built once for both files)
 
 
-@pytest.fixture(scope="module")
-def lane(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("lane_parent_equivalence") / "liblane_parent_equivalence.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-fopenmp", "-shared", "-o", so, SRC])
-    os.environ.setdefault("OMP_NUM_THREADS", str(NTHREADS))
-    lib = ctypes.CDLL(so)
-    lib.lane_vm_window.restype = ctypes.c_int64
-    lib.lane_vm_window.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int,
-                                   ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
-    lib.lane_boards.restype = None
-    lib.lane_boards.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
-                                ctypes.c_void_p]
-    return lib
-
-
-def _ids(pieces):
-    return np.asarray(pieces, np.int32)
-
-
-def _run_boards(lib, R, pieces, cols):
-    cols = np.ascontiguousarray(cols, np.uint32)
-    out = np.zeros(7, np.int64)
-    ids = _ids(pieces)
-    lib.lane_boards(R, len(ids), ids.ctypes.data, cols.ctypes.data, cols.shape[0], out.ctypes.data)
-    return dict(mask_bad=int(out[0]), feat_bad=int(out[1]), dirty=int(out[2]), masks=int(out[3]),
-                waves_rescue=int(out[4]), waves=int(out[5]), waves_sharper_rescue_test=int(out[6]))
-
-
-@pytest.mark.parametrize("R,every,sets", [(20, 1, ("catalogue9",)), (20, 16, ("default",)),
-                                          (10, 16, ("default", "catalogue9")), (24, 16, ("default", "catalogue9"))])
+@pytest.mark.parametrize("R,every,sets", lane_tests.WINDOW_CASES)
 def test_valid_mask_window_patterns(lane, R, every, sets):
-    for name in sets:
-        ids = _ids(SETS[name])
-        rescued = np.zeros(16, np.int64)
-        checked = np.zeros(1, np.int64)
-        feat_bad = np.zeros(1, np.int64)
-        bad = lane.lane_vm_window(R, len(ids), ids.ctypes.data, 0x5EED05 + R, every, rescued.ctypes.data,
-                                  checked.ctypes.data, feat_bad.ctypes.data)
-        print("R=%d %s every=%d: %d masks compared, %d mismatches, %d feature mismatches, rescued placements per piece %s"
-              % (R, name, every, checked[0], bad, feat_bad[0], rescued[:len(ids)].tolist()))
-        assert checked[0] == (1 << 24) // every * 5 * len(ids)  # nothing left out
-        assert bad == 0 and feat_bad[0] == 0
-        assert (rescued[:len(ids)] > 0).all(), "set (i) never reached the rescue for some piece"
+    lane_tests.window_patterns(lane, 1, 10, R, every, sets)
 
 
-def _steady_state_cols(R, n_boards, seed):
-    B = 50000
-    env = orc.OracleVecEnv(10, R, B, pieces="standard7", auto_reset=True, seed=seed, nthreads=NTHREADS)
-    env2 = orc.OracleVecEnv(10, R, B, pieces="default", auto_reset=True, seed=seed + 1, nthreads=NTHREADS)
-    for _ in range(256):
-        env.step()
-        env2.step()
-    sh = np.arange(R + 4, dtype=np.uint32)[None, :, None]
-    got = []
-    while sum(len(g) for g in got) < n_boards:
-        for e in (env, env2):
-            e.step()
-            got.append((e.cells.astype(np.uint32) << sh).sum(axis=1, dtype=np.uint32))
-    return np.concatenate(got)[:n_boards]
+def test_window_patterns_eight_columns(lane):
+    lane_tests.window_patterns(lane, 1, 8, 20, 16, ("default", "catalogue9"))
 
 
-@pytest.mark.parametrize("R,n_boards", [(20, 2000000), (10, 250000), (24, 250000)])
+@pytest.mark.parametrize("R,n_boards", lane_tests.STEADY_CASES)
 def test_steady_state_boards(lane, R, n_boards):
-    cols = _steady_state_cols(R, n_boards, seed=4321 + R)
-    assert cols.shape == (n_boards, 10)
-    for name, pieces in SETS.items():
-        r = _run_boards(lane, R, pieces, cols)
-        print("R=%d %s: %s" % (R, name, r))
-        assert r["dirty"] == 0  # cap on skipped boards: 0
-        assert r["masks"] == n_boards * len(pieces)
-        assert r["mask_bad"] == 0 and r["feat_bad"] == 0
+    lane_tests.steady_state_boards(lane, 1, R, n_boards)
 
 
-def test_golden_boards(lane):
-    gdir = os.path.join(HERE, "golden")
-    g1 = np.load(os.path.join(gdir, "g1_placements_10x20.npz"))
-    g4 = np.load(os.path.join(gdir, "g4_edges.npz"))
-    boards = [g1["boards"]] + [g4[k][None, :] for k in g4.files if k.endswith("_board")]
-    cols = np.concatenate(boards).astype(np.uint64)
-    clean = cols[(cols >> np.uint64(20)).max(axis=1) == 0]
-    assert len(clean) > 0
-    for name, pieces in SETS.items():
-        r = _run_boards(lane, 20, pieces, clean.astype(np.uint32))
-        print("golden %s: %d of %d boards clean, %s" % (name, len(clean), len(cols), r))
-        assert r["dirty"] == 0 and r["masks"] == len(clean) * len(pieces)
-        assert r["mask_bad"] == 0 and r["feat_bad"] == 0
+def test_yardstick_is_the_oracle(lane):
+    lane_tests.yardstick_is_the_oracle(lane, 1)
