@@ -1,6 +1,7 @@
 // tetris_entry.hpp -- what a kernel of tetris_kernels.hip and the CPU entry of the same name in
 // tests/harness/core_host.cpp share beyond the lane logic of tetris_core.hpp: which template
-// instantiation runs for a geometry, the table blobs, and the per-env bodies that are not a step.
+// instantiation runs for a geometry, the table blobs, the per-env bodies that are not a step, and the
+// parameter blocks the C-ABI (tetris_abi.inc) fills for both.
 // The kernels add what only a GPU needs (LDS staging, ballots, paired stores, launch bounds).
 #pragma once
 #include "tetris_core.hpp"
@@ -229,3 +230,136 @@ TET_HD void numpy_bag_stream_env(const uint32_t* seeds, int n_pieces, int64_t L,
 }
 
 }  // namespace tet
+
+// ---- parameter blocks -------------------------------------------------------------------------------
+// What the C-ABI (tetris_abi.inc) fills and a launch takes: the kernels by value, the CPU entries by reference.
+namespace {  // (as the table blobs above: the kernels' mangled names carry these types)
+
+struct StepParams {
+  void* cols;              // tile-major board words (tet::plane_index)
+  uint64_t* meta;
+  const int32_t* action;   // NULL: built-in uniform random policy
+  int32_t* action_out;     // optional: the action each env played
+  const uint8_t* stream;
+  int32_t* cursor;
+  int64_t stream_len;
+  float* obs;
+  int32_t* reward;
+  uint8_t* done;
+  uint8_t* lines;
+  uint8_t* n_valid;
+  uint8_t* piece_next;
+  uint32_t* status;
+  // payload of the done/reset gather, written by the step itself when given: one 64-bit done
+  // mask per wavefront (bit = lane) and a copy of the wavefront's counter slot as of THIS step -- a
+  // consistent snapshot in memory no later step touches, so the exchange can run beside the next steps
+  unsigned long long* done_bits;
+  uint32_t* status_snapshot;
+  uint32_t B;
+  uint32_t env_offset;     // global env index of env 0 (mod 2^32)
+  // step index from device memory (HIP-graph replays: the kernel arguments of a captured launch are
+  // frozen, the step's hash keys must not be): when set, the keys are derived in the kernel from
+  // *step_counter + step_rel instead of taken from cfg
+  const uint64_t* step_counter;
+  uint64_t seed;
+  uint32_t step_rel;
+  tet::StepCfg cfg;
+  tet::SetTable tab;
+};
+
+struct StepManyParams {
+  StepParams one;        // pointers of step 0; per-step outputs advance by B elements per step
+  int32_t n_steps;
+  int32_t policy;        // 0 uniform random, 1 greedy on w
+  uint64_t seed;
+  uint64_t step_idx0;
+  float w[8];
+};
+
+struct ResetParams {
+  void* cols;
+  uint64_t* meta;
+  uint32_t* status;        // per-wave counters or NULL: an env whose replay stream is exhausted is counted as invalid
+  const uint8_t* reset_mask;
+  uint8_t* piece_out;
+  uint8_t* n_valid_out;
+  const uint8_t* stream;
+  int32_t* cursor;
+  int64_t stream_len;
+  int64_t B;
+  int64_t env_offset;
+  int32_t init_bag;
+  int32_t n_pieces;
+  int32_t R;
+  uint32_t key;
+  tet::SetTable tab;
+};
+
+struct RefreshParams {
+  const void* cols;
+  uint64_t* meta;
+  uint8_t* n_valid_out;
+  int64_t B;
+  int32_t R;
+  tet::SetTable tab;
+};
+
+struct AfterParams {
+  const void* cols;
+  const uint64_t* meta;
+  float* feats;
+  uint8_t* n_valid;
+  float* feats_all;
+  uint8_t* n_all;
+  int64_t B;
+  int64_t env_stride;  // in floats: distance between the matrices of consecutive envs
+  int64_t row_stride;  // in floats: distance between consecutive feature rows of one env
+  int32_t R;
+  int32_t a_max;
+  int32_t has_direct_by;
+  float direct_by[8];
+  tet::SetTable tab;
+};
+
+struct GreedyParams {
+  const void* cols;
+  const uint64_t* meta;
+  int32_t* best_action;
+  float* best_value;
+  float* fitness_all;
+  int64_t B;
+  int32_t R;
+  int32_t a_max;
+  float w[8];
+  tet::SetTable tab;
+};
+
+struct RolloutParams {
+  const void* cols;
+  const uint64_t* meta;
+  double* returns;  // [B][a_max]
+  int64_t B;
+  int64_t env_offset;
+  int32_t R;
+  int32_t a_max;
+  int32_t n_pieces;
+  int32_t length;
+  int32_t n;
+  int32_t policy;
+  uint32_t key;
+  const uint8_t* pieces;  // NULL, or uint8 [B][a_max][n][length]: the piece every step of every rollout draws
+  float w[8];
+  tet::SetTable tab;
+};
+
+// bound step call: everything that does not change between steps is prepared once
+struct TetrisStepCall {
+  uint64_t magic;
+  StepParams p{};
+  TetrisDesc desc;
+  uint64_t seed;
+  int32_t* action_out;  // written only when the built-in policy draws the action
+};
+constexpr uint64_t kStepCallMagic = 0x5445545249535343ull;  // "TETRISSC"
+
+}  // namespace

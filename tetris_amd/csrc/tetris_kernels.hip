@@ -1,4 +1,4 @@
-// tetris_kernels.hip -- gfx950 kernels + the C-ABI of include/tetris_hip.h.
+// tetris_kernels.hip -- gfx950 kernels + the C-ABI of include/tetris_hip.h (its text: tetris_abi.inc).
 //
 // One lane per env; column bitboards in tile-major HBM storage (tet::plane_index: the planes of a
 // wavefront's 64 envs back to back, one contiguous record per wave; 256 contiguous bytes (u32) or 512
@@ -16,9 +16,6 @@ namespace {
 
 using tet::SetTable;
 using tet::StepCfg;
-using tet::build_table;
-using tet::n_placements;
-using tet::check_desc;
 
 constexpr int kBlock = 256;
 
@@ -121,38 +118,6 @@ __device__ __forceinline__ unsigned wave_sum(int value_bits, int v) {
   }
   return total;
 }
-
-struct StepParams {
-  void* cols;              // tile-major board words (tet::plane_index)
-  uint64_t* meta;
-  const int32_t* action;   // NULL: built-in uniform random policy
-  int32_t* action_out;     // optional: the action each env played
-  const uint8_t* stream;
-  int32_t* cursor;
-  int64_t stream_len;
-  float* obs;
-  int32_t* reward;
-  uint8_t* done;
-  uint8_t* lines;
-  uint8_t* n_valid;
-  uint8_t* piece_next;
-  uint32_t* status;
-  // payload of the done/reset gather, written by the step itself when given: one 64-bit done
-  // mask per wavefront (bit = lane) and a copy of the wavefront's counter slot as of THIS step -- a
-  // consistent snapshot in memory no later step touches, so the exchange can run beside the next steps
-  unsigned long long* done_bits;
-  uint32_t* status_snapshot;
-  uint32_t B;
-  uint32_t env_offset;     // global env index of env 0 (mod 2^32)
-  // step index from device memory (HIP-graph replays: the kernel arguments of a captured launch are
-  // frozen, the step's hash keys must not be): when set, the keys are derived in the kernel from
-  // *step_counter + step_rel instead of taken from cfg
-  const uint64_t* step_counter;
-  uint64_t seed;
-  uint32_t step_rel;
-  StepCfg cfg;
-  SetTable tab;
-};
 
 // Access element `byte_off / sizeof(T)` of a wave-uniform array through a 32-bit BYTE offset:
 // base stays in SGPRs and the lane offset is one shared VGPR (global_load/store saddr form)
@@ -358,15 +323,6 @@ constexpr int after_waves(int want) {
   return sizeof(W) == 4 ? want : (want > TET_AFTER_WAVES64 ? TET_AFTER_WAVES64 : want);
 }
 
-struct StepManyParams {
-  StepParams one;        // pointers of step 0; per-step outputs advance by B elements per step
-  int32_t n_steps;
-  int32_t policy;        // 0 uniform random, 1 greedy on w
-  uint64_t seed;
-  uint64_t step_idx0;
-  float w[8];
-};
-
 // K consecutive env-steps of every env in ONE launch, for policies that live in the kernel
 // (uniform random / greedy linear): the board and meta stay in registers between steps, every
 // step's outputs are written to trajectory buffers [K][B]...; bit-identical to K launches of
@@ -455,25 +411,6 @@ __global__ __launch_bounds__(step_block<W>(), (POLICY == 0 ? step_waves<W, CR>()
   }
 }
 
-struct ResetParams {
-  void* cols;
-  uint64_t* meta;
-  uint32_t* status;        // per-wave counters or NULL: an env whose replay stream is exhausted is counted as invalid
-  const uint8_t* reset_mask;
-  uint8_t* piece_out;
-  uint8_t* n_valid_out;
-  const uint8_t* stream;
-  int32_t* cursor;
-  int64_t stream_len;
-  int64_t B;
-  int64_t env_offset;
-  int32_t init_bag;
-  int32_t n_pieces;
-  int32_t R;
-  uint32_t key;
-  SetTable tab;
-};
-
 template <typename W, int C, bool PACK>
 __global__ __launch_bounds__(kBlock) void reset_kernel(const ResetParams p) {
   __shared__ SetTable tab;
@@ -491,15 +428,6 @@ __global__ __launch_bounds__(kBlock) void reset_kernel(const ResetParams p) {
                              p.cursor, cur, p.piece_out, p.n_valid_out);
 }
 
-struct RefreshParams {
-  const void* cols;
-  uint64_t* meta;
-  uint8_t* n_valid_out;
-  int64_t B;
-  int32_t R;
-  SetTable tab;
-};
-
 template <typename W, int C, bool PACK>
 __global__ __launch_bounds__(kBlock) void refresh_kernel(const RefreshParams p) {
   __shared__ SetTable tab;
@@ -508,23 +436,6 @@ __global__ __launch_bounds__(kBlock) void refresh_kernel(const RefreshParams p) 
   if (i >= p.B) return;
   tet::refresh_env<W, C, PACK>(static_cast<const W*>(p.cols), p.meta, p.n_valid_out, p.B, i, tab, p.R);
 }
-
-struct AfterParams {
-  const void* cols;
-  const uint64_t* meta;
-  float* feats;
-  uint8_t* n_valid;
-  float* feats_all;
-  uint8_t* n_all;
-  int64_t B;
-  int64_t env_stride;  // in floats: distance between the matrices of consecutive envs
-  int64_t row_stride;  // in floats: distance between consecutive feature rows of one env
-  int32_t R;
-  int32_t a_max;
-  int32_t has_direct_by;
-  float direct_by[8];
-  SetTable tab;
-};
 
 // game.py:67-80.  One lane per env walks the static slots in reference order;
 // the k-th non-terminal placement lands in feats[i][k].
@@ -633,19 +544,6 @@ __global__ __launch_bounds__(kBlock, (after_waves<W, C>(TET_AFTER_WAVES))) void 
 }
 
 
-struct GreedyParams {
-  const void* cols;
-  const uint64_t* meta;
-  int32_t* best_action;
-  float* best_value;
-  float* fitness_all;
-  int64_t B;
-  int32_t R;
-  int32_t a_max;
-  float w[8];
-  SetTable tab;
-};
-
 // Tetris.get_best_policy / fitness (game.py:102-120) for every env: the fitness of every
 // placement (raw order, terminal included, like game.py:103) and the best NON-terminal action.
 // The [B][a_max][8] feature matrix never touches HBM.
@@ -677,24 +575,6 @@ __global__ __launch_bounds__(kBlock, (after_waves<W, C>(TET_GREEDY_WAVES))) void
   p.best_action[i] = pick.best_row;
   if (p.best_value) p.best_value[i] = pick.best;
 }
-
-struct RolloutParams {
-  const void* cols;
-  const uint64_t* meta;
-  double* returns;  // [B][a_max]
-  int64_t B;
-  int64_t env_offset;
-  int32_t R;
-  int32_t a_max;
-  int32_t n_pieces;
-  int32_t length;
-  int32_t n;
-  int32_t policy;
-  uint32_t key;
-  const uint8_t* pieces;  // NULL, or uint8 [B][a_max][n][length]: the piece every step of every rollout draws
-  float w[8];
-  SetTable tab;
-};
 
 // Tetris.perform_rollouts (game.py:150-160) as a fan-out: one lane per (env, first action) runs its
 // n rollouts back to back with the board in registers; nothing but the mean returns is written.
@@ -803,8 +683,8 @@ inline dim3 step_grid(int64_t B) { return dim3((unsigned)((B + step_block<W>() -
 // The kernels are templates on the column count, and one hipcc process compiling all of them takes
 // minutes, so the in-tree build (tetris_amd/build.py) compiles this file once per column count
 // (-DTET_PART=<C>: the kernels of that count behind tetris_part_<C>) plus once as the main unit
-// (-DTET_SPLIT_MAIN: the C-ABI, which reaches the column-specific launches through those entries),
-// in parallel, and links the objects.  Compiled alone with neither macro the file is a complete
+// (-DTET_SPLIT_MAIN: the C-ABI -- tetris_abi.inc on the backend at the end of this file -- which reaches the
+// column-specific launches through those entries), in parallel, and links the objects.  Compiled alone with neither macro the file is a complete
 // single-unit library (what the tools' experiment builds do).
 template <template <typename, int> class Launcher> struct LaunchId;
 // Which instantiation a geometry runs is tet::kernel_variant's choice (tetris_entry.hpp), for these launchers as
@@ -946,226 +826,28 @@ int dispatch(const TetrisDesc* d, const P& p, hipStream_t s) {
 
 #if !defined(TET_PART)
 // ---- C-ABI ---------------------------------------------------------------------------
-extern "C" {
-
-int tetris_hip_version(void) { return TETRIS_HIP_ABI_VERSION; }
-
-#if TET_STAMPS
-int tetris_debug_read_stamps(uint64_t* dst, int n_wgs) {
-  return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_stamps), sizeof(uint64_t) * kStampWords * (size_t)n_wgs, 0,
-                                  hipMemcpyDeviceToHost);
-}
+// The text of the C-ABI is tetris_abi.inc, shared with the CPU harness; this is the backend it runs on here.
+#ifndef TET_SRC_HASH
+#define TET_SRC_HASH "unknown"
 #endif
+namespace {
+namespace backend {
 
-const char* tetris_hip_error_string(int code) {
-  const char* own = tet::error_text(code);
-  return own ? own : (code > 0 ? hipGetErrorString((hipError_t)code) : "unknown error");
-}
+constexpr const char* kSourceHash = TET_SRC_HASH;
+const char* error_text(int code) { return hipGetErrorString((hipError_t)code); }
 
-int tetris_hip_supported_columns(int32_t* out, int cap) {
-  int n = 0;
-#define X(CC) if (out && n < cap) out[n] = CC; ++n;
-  TET_COLUMNS(X)
-#undef X
-  return n;
-}
+int launch(const TetrisDesc* d, const StepParams& p, void* s) { return dispatch<LaunchStep>(d, p, (hipStream_t)s); }
+int launch(const TetrisDesc* d, const StepManyParams& p, void* s) { return dispatch<LaunchStepMany>(d, p, (hipStream_t)s); }
+int launch(const TetrisDesc* d, const ResetParams& p, void* s) { return dispatch<LaunchReset>(d, p, (hipStream_t)s); }
+int launch(const TetrisDesc* d, const RefreshParams& p, void* s) { return dispatch<LaunchRefresh>(d, p, (hipStream_t)s); }
+int launch(const TetrisDesc* d, const AfterParams& p, void* s) { return dispatch<LaunchAfter>(d, p, (hipStream_t)s); }
+int launch(const TetrisDesc* d, const GreedyParams& p, void* s) { return dispatch<LaunchGreedy>(d, p, (hipStream_t)s); }
+int launch(const TetrisDesc* d, const RolloutParams& p, void* s) { return dispatch<LaunchRollouts>(d, p, (hipStream_t)s); }
 
-int tetris_hip_n_planes(const TetrisDesc* desc) {
-  const int rc = check_desc(desc);
-  if (rc) return rc;
-  return tet::n_planes(desc->num_columns, tet::board_packed(desc->word_bytes, desc->num_rows));
-}
-
-int64_t tetris_hip_board_words(const TetrisDesc* desc, int64_t B) {
-  const int rc = check_desc(desc);
-  if (rc) return rc;
-  if (B <= 0) return TETRIS_E_BATCH;
-  return tet::board_words(B, tet::n_planes(desc->num_columns, tet::board_packed(desc->word_bytes, desc->num_rows)));
-}
-
-int64_t tetris_hip_status_words(int64_t B) {
-  if (B <= 0) return 0;
-  // one 16-byte slot per wavefront, rounded up to the largest tile a stepping kernel may use
-  return 4 * (((B + 1023) / 1024) * 16);
-}
-
-int tetris_hip_n_placements(int32_t catalogue_id, int32_t num_columns) {
-  if (catalogue_id < 0 || catalogue_id >= TETRIS_N_CATALOGUE) return TETRIS_E_PIECES;
-  return n_placements(catalogue_id, num_columns);
-}
-
-int tetris_hip_desc_init(TetrisDesc* desc, int32_t num_columns, int32_t num_rows, const int32_t* piece_ids,
-                         int32_t n_pieces, const float* direct_by) {
-  return tet::desc_init(desc, num_columns, num_rows, piece_ids, n_pieces, direct_by);
-}
-
-int tetris_hip_reset(const TetrisDesc* desc, void* cols, uint64_t* meta, const uint8_t* reset_mask,
-                     uint8_t* piece_out, uint8_t* n_valid_out, const uint8_t* stream, int32_t* cursor,
-                     int64_t stream_len, uint32_t* status, int32_t init_bag, uint64_t seed, uint64_t step_idx,
-                     int64_t env_offset, int64_t B, void* hip_stream) {
-  int rc = check_desc(desc);
-  if (rc) return rc;
-  if (!cols || !meta) return TETRIS_E_NULL;
-  if (B <= 0) return TETRIS_E_BATCH;
-  if (stream && (!cursor || stream_len <= 0)) return TETRIS_E_STREAM;
-  ResetParams p{};
-  p.cols = cols;
-  p.meta = meta;
-  p.status = status;
-  p.reset_mask = reset_mask;
-  p.piece_out = piece_out;
-  p.n_valid_out = n_valid_out;
-  p.stream = stream;
-  p.cursor = cursor;
-  p.stream_len = stream_len;
-  p.B = B;
-  p.env_offset = env_offset;
-  p.init_bag = init_bag;
-  p.n_pieces = desc->n_pieces;
-  p.R = desc->num_rows;
-  p.key = tet::hash_key(seed, step_idx * 4u + 2u);
-  build_table(desc, &p.tab);
-  return dispatch<LaunchReset>(desc, p, (hipStream_t)hip_stream);
-}
-
-static int fill_step_params(StepParams& p, const TetrisDesc* desc, void* cols, uint64_t* meta, const int32_t* action,
-                            int32_t* action_out, const uint8_t* stream, int32_t* cursor, int64_t stream_len,
-                            float* obs, int32_t* reward, uint8_t* done, uint8_t* lines, uint8_t* n_valid_next,
-                            uint8_t* piece_next, uint32_t* status, int32_t auto_reset, uint64_t seed,
-                            uint64_t step_idx, int64_t env_offset, int64_t B, int64_t max_elems);
-
-int tetris_hip_step_many(const TetrisDesc* desc, void* cols, uint64_t* meta, int32_t n_steps, int32_t policy,
-                         const float* weights, int32_t* action_out, float* obs, int32_t* reward, uint8_t* done,
-                         uint8_t* lines, uint8_t* n_valid_next, uint8_t* piece_next, uint32_t* status,
-                         int32_t auto_reset, uint64_t seed, uint64_t step_idx0, int64_t env_offset, int64_t B,
-                         void* hip_stream) {
-  if (n_steps < 1 || policy < 0 || policy > 1 || (policy == 1 && !weights)) return TETRIS_E_BATCH;
-  StepManyParams q{};
-  int rc = fill_step_params(q.one, desc, cols, meta, nullptr, action_out, nullptr, nullptr, 0, obs, reward, done,
-                            lines, n_valid_next, piece_next, status, auto_reset, seed, step_idx0, env_offset, B,
-                            (int64_t)B * n_steps);
-  if (rc) return rc;
-  q.n_steps = n_steps;
-  q.policy = policy;
-  q.seed = seed;
-  q.step_idx0 = step_idx0;
-  for (int i = 0; i < 8; ++i) q.w[i] = weights ? weights[i] : 0.f;
-  return dispatch<LaunchStepMany>(desc, q, (hipStream_t)hip_stream);
-}
-
-int tetris_hip_step(const TetrisDesc* desc, void* cols, uint64_t* meta, const int32_t* action, int32_t* action_out,
-                    const uint8_t* stream, int32_t* cursor, int64_t stream_len, float* obs, int32_t* reward,
-                    uint8_t* done, uint8_t* lines, uint8_t* n_valid_next, uint8_t* piece_next, uint32_t* status,
-                    int32_t auto_reset, uint64_t seed, uint64_t step_idx, int64_t env_offset, int64_t B,
-                    void* hip_stream) {
-  StepParams p{};
-  int rc = fill_step_params(p, desc, cols, meta, action, action_out, stream, cursor, stream_len, obs, reward, done,
-                            lines, n_valid_next, piece_next, status, auto_reset, seed, step_idx, env_offset, B, B);
-  if (rc) return rc;
-  return dispatch<LaunchStep>(desc, p, (hipStream_t)hip_stream);
-}
-
-static int fill_step_params(StepParams& p, const TetrisDesc* desc, void* cols, uint64_t* meta, const int32_t* action,
-                            int32_t* action_out, const uint8_t* stream, int32_t* cursor, int64_t stream_len,
-                            float* obs, int32_t* reward, uint8_t* done, uint8_t* lines, uint8_t* n_valid_next,
-                            uint8_t* piece_next, uint32_t* status, int32_t auto_reset, uint64_t seed,
-                            uint64_t step_idx, int64_t env_offset, int64_t B, int64_t max_elems) {
-  int rc = check_desc(desc);
-  if (rc) return rc;
-  if (!cols || !meta || !reward || !done || !lines || !n_valid_next) return TETRIS_E_NULL;
-  if (B <= 0 || max_elems > 0x7FFFFFFF / 32) return TETRIS_E_BATCH;  // every byte offset (<= 32 B/element) fits 32 bits
-  if ((B + 63) / 64 * 64 * (int64_t)tet::kMaxCols * 8 > 0xFFFFFFFFll) return TETRIS_E_BATCH;  // ... and so do the board records
-  if (stream && (!cursor || stream_len <= 0)) return TETRIS_E_STREAM;
-  p.cols = cols;
-  p.meta = meta;
-  p.action = action;
-  p.action_out = action_out;
-  p.stream = stream;
-  p.cursor = cursor;
-  p.stream_len = stream_len;
-  p.obs = obs;
-  p.reward = reward;
-  p.done = done;
-  p.lines = lines;
-  p.n_valid = n_valid_next;
-  p.piece_next = piece_next;
-  p.status = status;
-  p.done_bits = nullptr;        // (the gather payload is attached per call: tetris_hip_step_call_run_gather)
-  p.status_snapshot = nullptr;
-  p.B = (uint32_t)B;
-  p.env_offset = (uint32_t)env_offset;
-  p.step_counter = nullptr;
-  p.seed = seed;
-  p.step_rel = 0;
-  tet::fill_step_cfg(p.cfg, desc, auto_reset, obs != nullptr);
-  tet::step_keys(seed, step_idx, p.cfg);
-  build_table(desc, &p.tab);
-  return TETRIS_OK;
-}
-
-// ---- bound step call: everything that does not change between steps is prepared once ------------
-struct TetrisStepCall {
-  uint64_t magic;
-  StepParams p{};
-  TetrisDesc desc;
-  uint64_t seed;
-  int32_t* action_out;  // written only when the built-in policy draws the action
-};
-constexpr uint64_t kStepCallMagic = 0x5445545249535343ull;  // "TETRISSC"
-
-int64_t tetris_hip_step_call_size(void) { return (int64_t)sizeof(TetrisStepCall); }
-
-int tetris_hip_step_call_init(void* call_, const TetrisDesc* desc, void* cols, uint64_t* meta, int32_t* action_out,
-                              const uint8_t* stream, int32_t* cursor, int64_t stream_len, float* obs, int32_t* reward,
-                              uint8_t* done, uint8_t* lines, uint8_t* n_valid_next, uint8_t* piece_next,
-                              uint32_t* status, int32_t auto_reset, uint64_t seed, int64_t env_offset, int64_t B) {
-  if (!call_) return TETRIS_E_NULL;
-  TetrisStepCall* call = static_cast<TetrisStepCall*>(call_);
-  call->magic = 0;
-  int rc = fill_step_params(call->p, desc, cols, meta, nullptr, nullptr, stream, cursor, stream_len, obs, reward, done,
-                            lines, n_valid_next, piece_next, status, auto_reset, seed, 0, env_offset, B, B);
-  if (rc) return rc;
-  call->desc = *desc;
-  call->seed = seed;
-  call->action_out = action_out;
-  call->magic = kStepCallMagic;
-  return TETRIS_OK;
-}
-
-// what the three runs share: the checks, then this step's action / action_out and keys into the bound parameters
-static int step_call_begin(void* call_, const int32_t* action, uint64_t step_idx, TetrisStepCall*& call) {
-  call = static_cast<TetrisStepCall*>(call_);
-  if (!call) return TETRIS_E_NULL;
-  if (call->magic != kStepCallMagic) return TETRIS_E_DESC;
-  call->p.action = action;
-  call->p.action_out = action ? nullptr : call->action_out;
-  tet::step_keys(call->seed, step_idx, call->p.cfg);
-  return TETRIS_OK;
-}
-
-int tetris_hip_step_call_run(void* call_, const int32_t* action, uint64_t step_idx, void* hip_stream) {
-  TetrisStepCall* call;
-  const int rc = step_call_begin(call_, action, step_idx, call);
-  if (rc) return rc;
-  return dispatch<LaunchStep>(&call->desc, call->p, (hipStream_t)hip_stream);
-}
-
-int tetris_hip_step_call_run_gather(void* call_, const int32_t* action, uint64_t step_idx, uint64_t* done_bits,
-                                    uint32_t* status_snapshot, void* hip_stream) {
-  TetrisStepCall* call;
-  const int rc = step_call_begin(call_, action, step_idx, call);
-  if (rc) return rc;
-  StepParams p = call->p;  // (a copy: the bound call itself stays free of the payload pointers)
-  p.done_bits = reinterpret_cast<unsigned long long*>(done_bits);
-  p.status_snapshot = status_snapshot;
-  return dispatch<LaunchStep>(&call->desc, p, (hipStream_t)hip_stream);
-}
-
-int tetris_hip_stream_link(void* from_stream, void* to_stream) {
-  // `to_stream` waits for everything enqueued on `from_stream` so far.  The event releases to DEVICE scope:
-  // producer and consumer run on the same GPU (the consumer is the RCCL kernel that reads the gather
-  // payload), so the system-scope cache write-back a default event carries is not needed -- that write-back
-  // is what made a recorded event cost the stepping stream tens of microseconds.
+int stream_link(void* from_stream, void* to_stream) {
+  // The event releases to DEVICE scope: producer and consumer run on the same GPU (the consumer is the RCCL
+  // kernel that reads the gather payload), so the system-scope cache write-back a default event carries is
+  // not needed -- that write-back is what made a recorded event cost the stepping stream tens of microseconds.
   hipEvent_t ev;
   hipError_t rc = hipEventCreateWithFlags(&ev, hipEventDisableTiming | hipEventReleaseToDevice);
   if (rc != hipSuccess) return (int)rc;
@@ -1175,180 +857,60 @@ int tetris_hip_stream_link(void* from_stream, void* to_stream) {
   return (int)(rc != hipSuccess ? rc : rc2);
 }
 
-#ifndef TET_SRC_HASH
-#define TET_SRC_HASH "unknown"
-#endif
-const char* tetris_hip_source_hash(void) { return TET_SRC_HASH; }
-
-int tetris_hip_step_call_run_counted(void* call_, const int32_t* action, const uint64_t* step_counter, uint32_t step_rel,
-                                     void* hip_stream) {
-  if (!step_counter) return TETRIS_E_NULL;
-  TetrisStepCall* call;
-  const int rc = step_call_begin(call_, action, 0, call);  // (the kernel derives the keys from the counter)
-  if (rc) return rc;
-  StepParams p = call->p;  // (a copy: the bound call itself stays usable for plain runs)
-  p.step_counter = step_counter;
-  p.step_rel = step_rel;
-  return dispatch<LaunchStep>(&call->desc, p, (hipStream_t)hip_stream);
-}
-
-int tetris_hip_pack_done_bits(const uint8_t* done, uint8_t* bits, int64_t B, void* hip_stream) {
-  if (!done || !bits) return TETRIS_E_NULL;
-  if (B <= 0) return TETRIS_E_BATCH;
-  hipLaunchKernelGGL(pack_done_bits_kernel, grid_for(B), dim3(kBlock), 0, (hipStream_t)hip_stream, done,
+int pack_done_bits(const uint8_t* done, uint8_t* bits, int64_t B, void* s) {
+  hipLaunchKernelGGL(pack_done_bits_kernel, grid_for(B), dim3(kBlock), 0, (hipStream_t)s, done,
                      reinterpret_cast<unsigned long long*>(bits), B);
   return (int)hipGetLastError();
 }
 
-int tetris_hip_counter_add(uint64_t* counter, uint64_t n, void* hip_stream) {
-  if (!counter) return TETRIS_E_NULL;
-  hipLaunchKernelGGL(counter_add_kernel, dim3(1), dim3(1), 0, (hipStream_t)hip_stream, counter, n);
+int counter_add(uint64_t* counter, uint64_t n, void* s) {
+  hipLaunchKernelGGL(counter_add_kernel, dim3(1), dim3(1), 0, (hipStream_t)s, counter, n);
   return (int)hipGetLastError();
 }
 
-int tetris_hip_afterstates(const TetrisDesc* desc, const void* cols, const uint64_t* meta, float* feats,
-                           uint8_t* n_valid, float* feats_all, uint8_t* n_all, int64_t env_stride,
-                           int64_t row_stride, int64_t B, void* hip_stream) {
-  int rc = check_desc(desc);
-  if (rc) return rc;
-  if (!cols || !meta || !feats || !n_valid) return TETRIS_E_NULL;
-  if (B <= 0) return TETRIS_E_BATCH;
-  AfterParams p{};
-  p.cols = cols;
-  p.meta = meta;
-  p.feats = feats;
-  p.n_valid = n_valid;
-  p.feats_all = feats_all;
-  p.n_all = n_all;
-  p.B = B;
-  if (env_stride % 4 || row_stride % 4 || env_stride < 8 || row_stride < 8) return TETRIS_E_STRIDE;
-  // the kernel addresses rows with 32-bit float4 indices
-  if ((B - 1) * (env_stride / 4) + (int64_t)(desc->a_max - 1) * (row_stride / 4) + 2 >= 0xFFFFFFFFll) return TETRIS_E_STRIDE;
-  p.env_stride = env_stride;
-  p.row_stride = row_stride;
-  p.R = desc->num_rows;
-  p.a_max = desc->a_max;
-  p.has_direct_by = desc->has_direct_by;
-  for (int i = 0; i < 8; ++i) p.direct_by[i] = desc->direct_by[i];
-  build_table(desc, &p.tab);
-  return dispatch<LaunchAfter>(desc, p, (hipStream_t)hip_stream);
-}
-
-int tetris_hip_policy_greedy(const TetrisDesc* desc, const void* cols, const uint64_t* meta, const float* weights,
-                             int32_t* best_action, float* best_value, float* fitness_all, int64_t B,
-                             void* hip_stream) {
-  int rc = check_desc(desc);
-  if (rc) return rc;
-  if (!cols || !meta || !weights || !best_action) return TETRIS_E_NULL;
-  if (B <= 0) return TETRIS_E_BATCH;
-  GreedyParams p{};
-  p.cols = cols;
-  p.meta = meta;
-  p.best_action = best_action;
-  p.best_value = best_value;
-  p.fitness_all = fitness_all;
-  p.B = B;
-  p.R = desc->num_rows;
-  p.a_max = desc->a_max;
-  for (int i = 0; i < 8; ++i) p.w[i] = weights[i];
-  build_table(desc, &p.tab);
-  return dispatch<LaunchGreedy>(desc, p, (hipStream_t)hip_stream);
-}
-
-int tetris_hip_rollouts(const TetrisDesc* desc, const void* cols, const uint64_t* meta, double* returns,
-                        int32_t length, int32_t n, int32_t policy, const float* weights, const uint8_t* pieces,
-                        uint64_t seed, uint64_t step_idx, int64_t env_offset, int64_t B, void* hip_stream) {
-  int rc = check_desc(desc);
-  if (rc) return rc;
-  if (!cols || !meta || !returns || (policy == 1 && !weights)) return TETRIS_E_NULL;
-  if (B <= 0 || length < 1 || n < 1 || policy < 0 || policy > 1) return TETRIS_E_BATCH;
-  RolloutParams p{};
-  p.cols = cols;
-  p.meta = meta;
-  p.returns = returns;
-  p.B = B;
-  p.env_offset = env_offset;
-  p.R = desc->num_rows;
-  p.a_max = desc->a_max;
-  p.n_pieces = desc->n_pieces;
-  p.length = length;
-  p.n = n;
-  p.policy = policy;
-  p.pieces = pieces;
-  p.key = tet::hash_key(seed ^ 0x526F6C6C6F757473ull, step_idx);
-  for (int i = 0; i < 8; ++i) p.w[i] = weights ? weights[i] : 0.f;
-  build_table(desc, &p.tab);
-  return dispatch<LaunchRollouts>(desc, p, (hipStream_t)hip_stream);
-}
-
-int tetris_hip_refresh(const TetrisDesc* desc, const void* cols, uint64_t* meta, uint8_t* n_valid_out,
-                       int64_t B, void* hip_stream) {
-  int rc = check_desc(desc);
-  if (rc) return rc;
-  if (!cols || !meta) return TETRIS_E_NULL;
-  if (B <= 0) return TETRIS_E_BATCH;
-  RefreshParams p{};
-  p.cols = cols;
-  p.meta = meta;
-  p.n_valid_out = n_valid_out;
-  p.B = B;
-  p.R = desc->num_rows;
-  build_table(desc, &p.tab);
-  return dispatch<LaunchRefresh>(desc, p, (hipStream_t)hip_stream);
-}
-
-int tetris_hip_policy_random(const uint8_t* n_valid, int32_t* action, uint64_t seed, uint64_t step_idx,
-                             int64_t env_offset, int64_t B, void* hip_stream) {
-  if (!n_valid || !action) return TETRIS_E_NULL;
-  if (B <= 0) return TETRIS_E_BATCH;
-  const uint32_t key = tet::hash_key(seed, step_idx * 4u + 3u);
-  hipLaunchKernelGGL(policy_random_kernel, grid_for(B), dim3(kBlock), 0, (hipStream_t)hip_stream, n_valid,
-                     action, key, env_offset, B);
+int policy_random(const uint8_t* n_valid, int32_t* action, uint32_t key, int64_t env_offset, int64_t B, void* s) {
+  hipLaunchKernelGGL(policy_random_kernel, grid_for(B), dim3(kBlock), 0, (hipStream_t)s, n_valid, action, key,
+                     env_offset, B);
   return (int)hipGetLastError();
 }
 
-int tetris_hip_numpy_bag_stream(const uint32_t* seeds, int32_t n_pieces, int64_t L, uint8_t* stream, int64_t B,
-                                void* hip_stream) {
-  if (!seeds || !stream) return TETRIS_E_NULL;
-  if (n_pieces < 1 || n_pieces > TETRIS_MAX_PIECES) return TETRIS_E_PIECES;
-  if (B <= 0 || L <= 0) return TETRIS_E_BATCH;
-  hipLaunchKernelGGL(numpy_bag_stream_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, (hipStream_t)hip_stream,
-                     seeds, n_pieces, L, stream, B);
+int numpy_bag_stream(const uint32_t* seeds, int32_t n_pieces, int64_t L, uint8_t* stream, int64_t B, void* s) {
+  hipLaunchKernelGGL(numpy_bag_stream_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, (hipStream_t)s, seeds,
+                     n_pieces, L, stream, B);
   return (int)hipGetLastError();
 }
 
-int tetris_hip_decode(const TetrisDesc* desc, const void* cols, int8_t* cells, int32_t* heights, int64_t B,
-                      void* hip_stream) {
-  int rc = check_desc(desc);
-  if (rc) return rc;
-  if (!cols) return TETRIS_E_NULL;
-  if (B <= 0) return TETRIS_E_BATCH;
-  const int C = desc->num_columns, rows = desc->num_rows + 4;
-  const bool packed = tet::board_packed(desc->word_bytes, desc->num_rows);
-  if (desc->word_bytes == 4)
-    hipLaunchKernelGGL((decode_kernel<uint32_t>), grid_for(B), dim3(kBlock), 0, (hipStream_t)hip_stream,
+int decode(int word_bytes, const void* cols, int8_t* cells, int32_t* heights, int C, int rows, int64_t B,
+                  bool packed, void* s) {
+  if (word_bytes == 4)
+    hipLaunchKernelGGL((decode_kernel<uint32_t>), grid_for(B), dim3(kBlock), 0, (hipStream_t)s,
                        static_cast<const uint32_t*>(cols), cells, heights, C, rows, B, packed);
   else
-    hipLaunchKernelGGL((decode_kernel<uint64_t>), grid_for(B), dim3(kBlock), 0, (hipStream_t)hip_stream,
+    hipLaunchKernelGGL((decode_kernel<uint64_t>), grid_for(B), dim3(kBlock), 0, (hipStream_t)s,
                        static_cast<const uint64_t*>(cols), cells, heights, C, rows, B, packed);
   return (int)hipGetLastError();
 }
 
-int tetris_hip_encode(const TetrisDesc* desc, const int8_t* cells, void* cols, int64_t B, void* hip_stream) {
-  int rc = check_desc(desc);
-  if (rc) return rc;
-  if (!cols || !cells) return TETRIS_E_NULL;
-  if (B <= 0) return TETRIS_E_BATCH;
-  const int C = desc->num_columns, rows = desc->num_rows + 4;
-  const bool packed = tet::board_packed(desc->word_bytes, desc->num_rows);
-  if (desc->word_bytes == 4)
-    hipLaunchKernelGGL((encode_kernel<uint32_t>), grid_for(B), dim3(kBlock), 0, (hipStream_t)hip_stream, cells,
+int encode(int word_bytes, const int8_t* cells, void* cols, int C, int rows, int64_t B, bool packed, void* s) {
+  if (word_bytes == 4)
+    hipLaunchKernelGGL((encode_kernel<uint32_t>), grid_for(B), dim3(kBlock), 0, (hipStream_t)s, cells,
                        static_cast<uint32_t*>(cols), C, rows, B, packed);
   else
-    hipLaunchKernelGGL((encode_kernel<uint64_t>), grid_for(B), dim3(kBlock), 0, (hipStream_t)hip_stream, cells,
+    hipLaunchKernelGGL((encode_kernel<uint64_t>), grid_for(B), dim3(kBlock), 0, (hipStream_t)s, cells,
                        static_cast<uint64_t*>(cols), C, rows, B, packed);
   return (int)hipGetLastError();
 }
 
-}  // extern "C"
+}  // namespace backend
+}  // namespace
+
+#define TET_ABI(name) tetris_hip_##name
+#include "tetris_abi.inc"
+
+#if TET_STAMPS
+extern "C" int tetris_debug_read_stamps(uint64_t* dst, int n_wgs) {
+  return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_stamps), sizeof(uint64_t) * kStampWords * (size_t)n_wgs, 0,
+                                  hipMemcpyDeviceToHost);
+}
+#endif
 #endif  // !TET_PART
