@@ -242,6 +242,10 @@ TET_HD int popc(uint64_t x) { return __builtin_popcountll(x); }
 // used (stored rows < bits(W)), so (x << 1) | 1 is a non-zero word one bit longer: no select.
 TET_HD int bitlen(uint32_t x) { return 31 - __builtin_clz((x << 1) | 1u); }
 TET_HD int bitlen(uint64_t x) { return 63 - __builtin_clzll((x << 1) | 1ull); }
+TET_HD uint32_t umin(uint32_t a, uint32_t b) { return a < b ? a : b; }
+// the count itself: bits(W) - 1 - bitlen(x)
+TET_HD int nlz_above(uint32_t x) { return __builtin_clz((x << 1) | 1u); }
+TET_HD int nlz_above(uint64_t x) { return __builtin_clzll((x << 1) | 1ull); }
 // (1 << n) - 1 for 0 <= n < bits(W)   (stored rows < bits(W) by contract)
 template <typename W>
 TET_HD W lowmask(int n) { return (W)(((W)1 << n) - 1); }
@@ -359,9 +363,26 @@ struct alignas(16) OrientEntry {  // 48 bytes = three 16-byte LDS reads (field o
 };
 static_assert(sizeof(OrientEntry) == 48, "table staging and LDS reads assume 48-byte entries");
 
+// What the stamp of the CHOSEN placement needs of its orientation, ready to use (one 16-byte LDS read
+// behind the decoded slot): the step kernel is bound by vector issue alone, and taking w, b_j, n_j out of
+// `desc` costs a bit-field extract each, of the slow issue class.  One byte per
+// footprint column j, so that a byte select of the consuming instruction (SDWA) picks the field:
+//   shape4 byte j = lowmask(n_j) << b_j  (<= 15; 0 for j >= w):  cells of column j = byte << anchor row
+//   bias4  byte j = b_j, or kNoColumn for j >= w: the landing row is top - min_j(clz(column) + bias), and a
+//                   column that adds kNoColumn can never be that minimum
+struct alignas(16) StampRow {
+  uint32_t shape4;
+  uint32_t bias4;
+  uint32_t H;          // piece height (BCTS landing height)
+  uint32_t pad_;
+};
+constexpr uint32_t kNoColumn = 64;  // > clz of any board word
+static_assert(sizeof(StampRow) == 16, "one ds_read_b128");
+
 struct SetTable {
   OrientEntry orient[kMaxPieces][4];
   uint64_t fullmask[kMaxPieces];   // all existing placements (every one valid)
+  StampRow stamp[kMaxPieces][4];   // same index as orient
 };
 
 // The four entries of piece `np`.  The byte offset is laundered through a register so that the
@@ -1007,31 +1028,46 @@ TET_HD int stamp_dynamic(W (&col)[C], const int (&h)[C], int c, uint32_t d, W (&
 // of selecting among registers: 10 stores, 4 loads, 4 ORs, 10 loads replace ~150 VALU selects,
 // and only the four footprint heights are computed.  (The kernels are integer-VALU bound and
 // the LDS pipe is otherwise idle.)
-template <typename W, int C>
-TET_HD int stamp_scratch(W (&col)[C], W* scratch, int sstride, int c, uint32_t d, W (&pbits)[4]) {
+// The orientation arrives as its StampRow: a byte per footprint column, so no field is extracted from the
+// descriptor and there is no "j < w" select -- the landing row is top - min_j(leading zeros of the column +
+// b_j), where an absent column adds kNoColumn and cannot be the minimum, and the cells of column j are
+// its shape byte moved up by the landing row.
+// PAD: the scratch array has scratch_cols = C + 3 columns, so the four footprint columns c .. c+3 are one
+// base address + constant offsets with no clamp.  The columns beyond the board take ORs of zero (they
+// belong to no footprint: fullmask) and what they hold is never used.  Without PAD the index is clamped.
+// c must be < C (slot_of_action_lut returns columns of set mask bits only; env_step bounds it once more).
+template <typename W, int C, bool PAD = false>
+TET_HD int stamp_scratch(W (&col)[C], W* scratch, int sstride, int c, const StampRow& row, W (&pbits)[4]) {
 #pragma unroll
   for (int i = 0; i < C; ++i) scratch[i * sstride] = col[i];
-  const int w = d & 7;
-  int a = 0;
+  const uint32_t shape4 = row.shape4, bias4 = row.bias4;
+  constexpr uint32_t kTop = 8 * (uint32_t)sizeof(W) - 1;
+  uint32_t v[4];
   int idx[4];
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
-    idx[j] = (c + j < C ? c + j : C - 1) * sstride;
-    const int bj = (d >> (6 + 5 * j)) & 3;
-    const int v = bitlen(scratch[idx[j]]) - bj;
-    a = (j < w && v > a) ? v : a;
+    idx[j] = (PAD ? c + j : (c + j < C ? c + j : C - 1)) * sstride;
+    v[j] = (uint32_t)nlz_above(scratch[idx[j]]) + ((bias4 >> (8 * j)) & 255u);  // = top - (h - b_j)
   }
+  // two three-input minima; kTop bounds the row at 0 for a slot that has no orientation (all kNoColumn)
+  const uint32_t m012 = umin(umin(v[0], v[1]), v[2]);
+  const uint32_t m = umin(umin(m012, v[3]), kTop);
+  const int a = (int)(kTop - m);
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
-    const int bj = (d >> (6 + 5 * j)) & 3;
-    const int nj = (int)((d >> (8 + 5 * j)) & 7);  // 0 for j >= w (pack_orient leaves those fields empty)
-    pbits[j] = (W)(lowmask<W>(nj) << (a + bj));    // one v_bfm_b32 on 32-bit boards
-    TET_SCRATCH_OR(&scratch[idx[j]], pbits[j]);    // j >= w ORs zero (index clamped in range)
+    pbits[j] = (W)((W)((shape4 >> (8 * j)) & 255u) << a);
+    TET_SCRATCH_OR(&scratch[idx[j]], pbits[j]);    // j >= w ORs zero
   }
 #pragma unroll
   for (int i = 0; i < C; ++i) col[i] = scratch[i * sstride];
   return a;
 }
+// columns of the per-lane scratch array the stepping kernels give stamp_scratch (they pass scratch_padded to
+// env_step as SPAD): padded where the small tables leave the LDS room (the forms that run board_features_u32_2x10)
+template <typename W, int C, int NCH, int CR, bool PACKW = false>
+TET_HD constexpr bool scratch_padded() { return features_packed<W, C, NCH, CR, PACKW>(); }
+template <typename W, int C, int NCH, int CR, bool PACKW = false>
+TET_HD constexpr int scratch_cols() { return scratch_padded<W, C, NCH, CR, PACKW>() ? C + 3 : C; }
 
 // ---- all afterstates of one env (game.py:67-80) -----------------------------------------
 // emit(has, field k = 2L + o, column c, f[8], row_all, row_valid, is_valid) is called for every placement
@@ -1307,7 +1343,9 @@ TET_HD int policy_random(uint32_t key_policy, uint32_t env, int n_valid) {
 // `action` < 0 with use_policy: draw it with policy_random.  `draw` = replay piece for the
 // step draw (or -1: use the bag), `draw_reset` = replay piece for the reset draw (or -1).
 // PACKW: hole_lut is an AfterLut (kernels whose policy walks the afterstates) instead of a LutLayout<CR>
-template <typename W, int C, int NCH = 0, int CR = 12, bool PACKW = false>
+// SPAD: the caller's scratch array has C + 3 columns (tet::scratch_cols) and the stamp runs unclamped; the
+// caller says so, so that a caller with a plain C-column array (the CPU harness, the rollouts) stays right
+template <typename W, int C, int NCH = 0, int CR = 12, bool PACKW = false, bool SPAD = false>
 TET_HD void env_step(W (&col)[C], uint64_t& meta, int action, bool use_policy, const SetTable& tab,
                      const uint8_t* hole_lut, W* scratch, int sstride, const StepCfg& cfg, uint32_t env, int draw,
                      int draw_reset, StepOut& out) {
@@ -1331,13 +1369,24 @@ TET_HD void env_step(W (&col)[C], uint64_t& meta, int action, bool use_policy, c
   }
   // decode action -> (orientation field, left column): game.py:69,83
   int sk, c;
+  if (TET_ABLATE & 4096) {  // timing-only: no action decode
+    sk = action & 1;
+    c = action & 3;
+  } else
   slot_of_action_lut<C>(mask, action, hole_lut + (PACKW ? AfterLut::kSelPair : LutLayout<CR>::kSelPair), sk, c);
-  const uint32_t od = tab.orient[piece][sk].desc;
-  const int oH = (od >> 3) & 7;
+  const StampRow& srow = tab.stamp[piece][sk];
+  const int oH = (int)srow.H;
+  if (SPAD) c = c < C ? c : C - 1;  // the unclamped scratch index stays inside its C + 3 columns whatever the mask word held
 
   int h[C];
   W pbits[4];
-  const int a = stamp_scratch<W, C>(col, scratch, sstride, c, od, pbits);  // tetromino.py get_after_states
+  int a;
+  if (TET_ABLATE & 2048) {  // timing-only: no stamp
+    a = c;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) pbits[j] = (W)(srow.shape4 >> (8 * j));
+  } else
+  a = stamp_scratch<W, C, SPAD>(col, scratch, sstride, c, srow, pbits);  // tetromino.py get_after_states
   int eroded = 0;
   const int k = (TET_ABLATE & 8) ? 0 : clear_lines<W, C>(col, pbits, a, &eroded);   // state.py:33
   heights_of<W, C>(col, h);

@@ -352,6 +352,10 @@ struct RolloutParams {
   tet::SetTable tab;
 };
 
+// the blocks travel as kernel arguments (4 KiB at the most), the table inside them
+static_assert(sizeof(StepManyParams) <= 4096 && sizeof(RolloutParams) <= 4096 && sizeof(AfterParams) <= 4096 &&
+              sizeof(GreedyParams) <= 4096 && sizeof(ResetParams) <= 4096, "kernel argument block over 4 KiB");
+
 // bound step call: everything that does not change between steps is prepared once
 struct TetrisStepCall {
   uint64_t magic;

@@ -79,7 +79,8 @@ struct alignas(16) StepLds {
   // (NCH = 2 is the only chunk count 32-bit boards run with the 10-row tables)
   alignas(16) uint8_t lut[AFTER ? tet::kAfterLutBytes
                                 : (tet::features_packed<W, C, 2, CR>() ? tet::LutLayout<CR>::kBytes : tet::LutLayout<CR>::kByteTablesEnd)];
-  W lane_cols[C][BLK];  // per-lane scratch for the runtime-indexed stamp (bank = lane)
+  // per-lane scratch for the runtime-indexed stamp (bank = lane); C + 3 columns where tet::stamp_scratch runs unclamped
+  W lane_cols[tet::scratch_cols<W, C, 2, CR, AFTER>()][BLK];
 };
 
 // The part of the feature tables a stepping kernel reads, in 16-byte units [begin, end): the byte tables and
@@ -118,6 +119,9 @@ __device__ __forceinline__ unsigned wave_sum(int value_bits, int v) {
   }
   return total;
 }
+// number of lanes of the wave for which `cond` holds: the comparison result feeds the ballot as it is
+// (no 0 / 1 integer is built per lane and tested again)
+__device__ __forceinline__ unsigned wave_count(bool cond) { return (unsigned)__popcll(__ballot(cond)); }
 
 // Access element `byte_off / sizeof(T)` of a wave-uniform array through a 32-bit BYTE offset:
 // base stays in SGPRs and the lane offset is one shared VGPR (global_load/store saddr form)
@@ -189,7 +193,8 @@ __global__ __launch_bounds__(BLK, (step_waves<W, CR>())) void step_kernel(const 
   __shared__ StepLds<W, C, kBlock, CR> lds;
   SetTable& tab = lds.tab;
   uint8_t* const hole_lut = lds.lut;
-  W (&lane_cols)[C][kBlock] = lds.lane_cols;
+  auto& lane_cols = lds.lane_cols;
+  static_assert(sizeof(lds.lane_cols) / sizeof(lds.lane_cols[0]) >= (tet::scratch_padded<W, C, NCH, CR, false>() ? C + 3 : C), "the unclamped stamp needs its three columns");
   const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
   const bool live = i < p.B;
   // Issue every global load of this lane first (board, meta, action, counters, its share of the
@@ -232,13 +237,14 @@ __global__ __launch_bounds__(BLK, (step_waves<W, CR>())) void step_kernel(const 
     cfg.key_step = tet::hash_key(p.seed, idx * 4u + 0u);  // (== tet::step_keys, written out: tetris_entry.hpp)
     cfg.key_policy = tet::hash_key(p.seed, idx * 4u + 3u);
   }
-  int invalid = 0, done = 0, lines = 0, done_flag = 0;
+  bool invalid = false, done = false, done_flag = false;
+  int lines = 0;
   if (live) {
     tet::StepOut out;
-    tet::env_step<W, C, NCH, CR>(in.col, in.meta, in.exhausted ? -1 : in.action, p.action == nullptr && !in.exhausted,
+    tet::env_step<W, C, NCH, CR, false, tet::scratch_padded<W, C, NCH, CR>()>(in.col, in.meta, in.exhausted ? -1 : in.action, p.action == nullptr && !in.exhausted,
                              tab, hole_lut, &lane_cols[0][threadIdx.x], kBlock, cfg, p.env_offset + i, in.draw,
                              in.draw_reset, out);
-    invalid = out.invalid;
+    invalid = out.invalid != 0;
     TET_STAMP(2);
     if (p.obs) {
       float4* o4 = reinterpret_cast<float4*>(p.obs);
@@ -248,11 +254,11 @@ __global__ __launch_bounds__(BLK, (step_waves<W, CR>())) void step_kernel(const 
     if (!invalid) {
       store_planes<W, C, PACK>(p, i, in.col);
       st_off(p.meta, i * 8u, in.meta);
-      done = out.done;
+      done = out.done != 0;
       lines = out.lines;
       if (p.stream) p.cursor[i] = in.cursor + 1 + ((out.done && cfg.auto_reset) ? 1 : 0);  // (== tet::stream_advance)
     }
-    done_flag = out.done;  // what the done array holds (an env that was already over reports done again)
+    done_flag = out.done != 0;  // what the done array holds (an env that was already over reports done again)
     st_off(p.reward, i * 4u, (int32_t)out.reward);
     st_off(p.done, i, (uint8_t)out.done);
     st_off(p.lines, i, (uint8_t)out.lines);
@@ -260,12 +266,12 @@ __global__ __launch_bounds__(BLK, (step_waves<W, CR>())) void step_kernel(const 
     if (p.piece_next) st_off(p.piece_next, i, (uint8_t)out.piece);
     if (p.action_out) st_off(p.action_out, i * 4u, (int32_t)out.action);
   }
-  if (p.status || p.done_bits) {
-    const unsigned long long done_mask = __ballot(done_flag != 0);  // == tetris_hip_pack_done_bits(done)
-    const unsigned n_inv = wave_sum(1, invalid);
-    const unsigned n_done = wave_sum(1, done);
+  if (!(TET_ABLATE & 8192) && (p.status || p.done_bits)) {
+    const unsigned long long done_mask = __ballot(done_flag);  // == tetris_hip_pack_done_bits(done)
+    const unsigned n_inv = wave_count(invalid);
+    const unsigned n_done = wave_count(done);
     const unsigned n_lines = wave_sum(3, lines);
-    const unsigned n_steps = wave_sum(1, (live && !invalid) ? 1 : 0);
+    const unsigned n_steps = wave_count(live && !invalid);
     if ((threadIdx.x & 63) == 0) {
       uint4 v = in.status;
       v.x += n_inv;
@@ -336,7 +342,8 @@ __global__ __launch_bounds__(step_block<W>(), (POLICY == 0 ? step_waves<W, CR>()
   __shared__ StepLds<W, C, kBlock, CR, AFTER> lds;
   SetTable& tab = lds.tab;
   uint8_t* const hole_lut = lds.lut;
-  W (&lane_cols)[C][kBlock] = lds.lane_cols;
+  auto& lane_cols = lds.lane_cols;
+  static_assert(sizeof(lds.lane_cols) / sizeof(lds.lane_cols[0]) >= (tet::scratch_padded<W, C, NCH, CR, AFTER>() ? C + 3 : C), "the unclamped stamp needs its three columns");
   const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
   const bool live = i < p.B;
   constexpr bool PACK = NCH != 0 && !TET_NO_PACK;
@@ -351,7 +358,8 @@ __global__ __launch_bounds__(step_block<W>(), (POLICY == 0 ? step_waves<W, CR>()
   for (int k = 0; k < q.n_steps; ++k) {
     cfg.key_step = tet::hash_key(q.seed, (q.step_idx0 + (uint64_t)k) * 4u + 0u);  // (== tet::step_keys)
     cfg.key_policy = tet::hash_key(q.seed, (q.step_idx0 + (uint64_t)k) * 4u + 3u);
-    int invalid = 0, done = 0, lines = 0;
+    bool invalid = false, done = false;
+    int lines = 0;
     if (live) {
       int action = -1;
       bool use_policy = true;
@@ -372,9 +380,9 @@ __global__ __launch_bounds__(step_block<W>(), (POLICY == 0 ? step_waves<W, CR>()
         use_policy = false;
       }
       tet::StepOut out;
-      tet::env_step<W, C, NCH, CR, AFTER>(in.col, in.meta, action, use_policy, tab, hole_lut, &lane_cols[0][threadIdx.x],
+      tet::env_step<W, C, NCH, CR, AFTER, tet::scratch_padded<W, C, NCH, CR, AFTER>()>(in.col, in.meta, action, use_policy, tab, hole_lut, &lane_cols[0][threadIdx.x],
                                           kBlock, cfg, p.env_offset + i, -1, -1, out);
-      invalid = out.invalid;
+      invalid = out.invalid != 0;
       const uint32_t e = (uint32_t)k * p.B + i;  // element index in the [K][B] trajectory buffers
       if (p.obs) {
         float4* o4 = reinterpret_cast<float4*>(p.obs);
@@ -382,7 +390,7 @@ __global__ __launch_bounds__(step_block<W>(), (POLICY == 0 ? step_waves<W, CR>()
         st_off(o4, e * 32u + 16u, make_float4(out.obs[4], out.obs[5], out.obs[6], out.obs[7]));
       }
       if (!invalid) {
-        done = out.done;
+        done = out.done != 0;
         lines = out.lines;
       }
       st_off(p.reward, e * 4u, (int32_t)out.reward);
@@ -392,10 +400,10 @@ __global__ __launch_bounds__(step_block<W>(), (POLICY == 0 ? step_waves<W, CR>()
       if (p.piece_next) st_off(p.piece_next, e, (uint8_t)out.piece);
       if (p.action_out) st_off(p.action_out, e * 4u, (int32_t)out.action);
     }
-    n_inv += wave_sum(1, invalid);
-    n_done += wave_sum(1, done);
+    n_inv += wave_count(invalid);
+    n_done += wave_count(done);
     n_lines += wave_sum(3, lines);
-    n_steps += wave_sum(1, (live && !invalid) ? 1 : 0);
+    n_steps += wave_count(live && !invalid);
   }
   if (live) {
     store_planes<W, C, PACK>(p, i, in.col);
@@ -586,7 +594,7 @@ __global__ __launch_bounds__(kRolloutBlock, (after_waves<W, C>(TET_STEP_GREEDY_W
   __shared__ StepLds<W, C, kBlock, 12, true> lds;
   SetTable& tab = lds.tab;
   uint8_t* const hole_lut = lds.lut;
-  W (&lane_cols)[C][kBlock] = lds.lane_cols;
+  auto& lane_cols = lds.lane_cols;
   stage_after_lut(hole_lut);
   stage_table(tab, p.tab);
   const int64_t id = (int64_t)blockIdx.x * kBlock + threadIdx.x;

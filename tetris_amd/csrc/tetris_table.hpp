@@ -83,9 +83,26 @@ inline void pack_mask_fields(const CatOrient& o, OrientEntry* e) {
   }
 }
 
+// the stamp's view of one orientation (tet::StampRow): a byte per footprint column
+inline void pack_stamp_row(const CatOrient& o, StampRow* s) {
+  s->shape4 = 0;
+  s->bias4 = 0;
+  s->H = 0;
+  s->pad_ = 0;
+  for (int j = 0; j < 4; ++j) {
+    const bool has = j < o.w;
+    const uint32_t shape = has ? (((1u << o.n[j]) - 1u) << o.b[j]) : 0u;
+    s->shape4 |= shape << (8 * j);
+    s->bias4 |= (has ? (uint32_t)o.b[j] : kNoColumn) << (8 * j);
+    if (has && (uint32_t)(o.b[j] + o.n[j]) > s->H) s->H = (uint32_t)(o.b[j] + o.n[j]);
+  }
+}
+
 inline void build_table(const TetrisDesc* d, SetTable* t) {
   memset(t, 0, sizeof(*t));
   const int C = d->num_columns;
+  for (int i = 0; i < kMaxPieces; ++i)  // slots without an orientation: no column (never stamped: fullmask has no such placement)
+    for (int k = 0; k < 4; ++k) t->stamp[i][k].bias4 = kNoColumn * 0x01010101u;
   for (int i = 0; i < d->n_pieces; ++i) {
     const CatPiece& p = kCatalogue[d->piece_ids[i]];
     uint64_t full = 0;
@@ -94,6 +111,7 @@ inline void build_table(const TetrisDesc* d, SetTable* t) {
         OrientEntry* e = &t->orient[i][l * 2 + oi];
         e->desc = pack_orient(p.o[l][oi]);
         pack_mask_fields(p.o[l][oi], e);
+        pack_stamp_row(p.o[l][oi], &t->stamp[i][l * 2 + oi]);
         for (int c = 0; c + p.o[l][oi].w <= C; ++c) full |= 1ull << mask_bit(2 * l + oi, c);
       }
     t->fullmask[i] = full;

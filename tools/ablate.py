@@ -2,7 +2,8 @@
 """Timing-only ablation of the step kernel: builds libtetris_hip variants with
 -DTET_ABLATE=<mask> (parts of the step removed -> wrong results, same memory
 traffic) and times the step kernel of each with HIP events, interleaved A/B in
-one process.  bit0 features, bit1 next-piece mask, bit3 clear, bit4 hole tables, bit5 wells, bit6 afterstates stores, bit7 table staging."""
+one process.  bit0 features, bit1 next-piece mask, bit3 clear, bit4 hole tables, bit5 wells, bit6 afterstates stores, bit7 table staging,
+bit11 (2048) stamp, bit12 (4096) action decode, bit13 (8192) the per-wave counters of the epilogue."""
 import ctypes
 import os
 import subprocess
