@@ -43,7 +43,7 @@
 extern "C" {
 #endif
 
-#define TETRIS_HIP_ABI_VERSION 6
+#define TETRIS_HIP_ABI_VERSION 7
 
 #define TETRIS_MAX_PIECES 12
 #define TETRIS_MAX_COLUMNS 12
@@ -64,7 +64,8 @@ enum {
   TETRIS_E_PIECES = -5,      /* bad piece list */
   TETRIS_E_BATCH = -6,       /* B <= 0 (tetris_hip_step: or B beyond ~53 M envs per call: 32-bit byte offsets) */
   TETRIS_E_STREAM = -7,      /* replay stream given without cursor / length */
-  TETRIS_E_STRIDE = -8       /* afterstate strides not multiples of 4 floats / too small / matrix beyond 2^32 float4 */
+  TETRIS_E_STRIDE = -8,      /* afterstate strides not multiples of 4 floats / too small / matrix beyond 2^32 float4 */
+  TETRIS_E_OVERLAP = -9      /* tetris_hip_gather_envs: source and destination storage overlap */
 };
 
 /* Constructor arguments of game.Tetris (game.py:21-23) that shape the kernels. */
@@ -326,6 +327,31 @@ int tetris_hip_encode(const TetrisDesc* desc, const int8_t* cells, void* cols, i
  * caller edits cols / meta directly, e.g. to restore a snapshot or set a board) */
 int tetris_hip_refresh(const TetrisDesc* desc, const void* cols, uint64_t* meta,
                        uint8_t* n_valid_out, int64_t B, void* hip_stream);
+
+/*
+ * Copy envs between two batches of one geometry by index: dst env j := src env index[j], on the stored
+ * representation.  The batch form of restoring `current_state` / `current_tetromino` by assignment
+ * (game.py:130-148): fork a position into a second batch, resample a population, restart finished envs
+ * from a bank of stored states.  Both batches share `desc`; src holds B_src envs, dst B_dst.
+ *  index[j] in [0, B_src) : every plane word of the board and all 64 bits of meta (valid mask, piece AND
+ *                           bag) are copied verbatim; dst_n_valid[j] = the number of non-terminal placements
+ *                           (the count tetris_hip_refresh / tetris_hip_afterstates report for that env:
+ *                           popcount of mask & fullmask[piece]) and dst_piece[j] = the piece
+ *  index[j] == -1         : dst env j is left untouched: no byte of its board, meta, n_valid or piece is written
+ *  any other value        : the env is left untouched and counted in status[TETRIS_STATUS_INVALID] of dst wave
+ *                           j / 64 (the lazy reporting of an out-of-range action)
+ *  index       : int32[B_dst]
+ *  dst_n_valid / dst_piece : uint8[B_dst], either may be NULL
+ *  status      : dst's per-wave counters (uint32[tetris_hip_status_words of B_dst]) or NULL
+ * The padding lanes of dst's last tile are never written.  src and dst storage must not overlap (the kernel
+ * reads scattered and writes in place, so a permutation in place would race): if the byte ranges of the two
+ * `cols` or of the two `meta` overlap the call returns TETRIS_E_OVERLAP before anything is launched; permute in
+ * place through a second cols / meta pair.  B_src, B_dst <= 0 or beyond the bound of tetris_hip_step:
+ * TETRIS_E_BATCH.  Replay streams (stream / cursor) are not part of this call.
+ */
+int tetris_hip_gather_envs(const TetrisDesc* desc, const void* src_cols, const uint64_t* src_meta, int64_t B_src,
+                           void* dst_cols, uint64_t* dst_meta, uint8_t* dst_n_valid, uint8_t* dst_piece,
+                           const int32_t* index, uint32_t* status, int64_t B_dst, void* hip_stream);
 
 #ifdef __cplusplus
 }

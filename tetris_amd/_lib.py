@@ -9,7 +9,7 @@ import os
 from . import build as _build
 
 MAX_PIECES = 12
-ABI_VERSION = 6
+ABI_VERSION = 7
 
 
 class TetrisDesc(ctypes.Structure):
@@ -65,6 +65,7 @@ SIGNATURES = {
     "tetris_hip_decode": [_dp, _vp, _vp, _vp, _i64, _vp],
     "tetris_hip_encode": [_dp, _vp, _vp, _i64, _vp],
     "tetris_hip_refresh": [_dp, _vp, _vp, _vp, _i64, _vp],
+    "tetris_hip_gather_envs": [_dp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp],
 }
 EXPORTS = list(SIGNATURES) + ["tetris_hip_error_string", "tetris_hip_source_hash"]
 

@@ -3,12 +3,19 @@
 // it for libtetris_hip.so, tests/harness/core_host.cpp for the CPU harness.  The includer defines
 //   TET_ABI(name)       the exported symbol: tetris_hip_##name / tetris_host_##name
 //   namespace backend   what differs between a GPU and a loop over envs, each returning an error code:
-//     launch(const TetrisDesc*, const XParams&, void* stream), overloaded on the seven parameter blocks;
+//     launch(const TetrisDesc*, const XParams&, void* stream), overloaded on the eight parameter blocks (the CPU
+//     harness takes GatherParams' from tetris_entry.hpp);
 //     pack_done_bits, counter_add, policy_random, numpy_bag_stream, decode, encode, stream_link (the arguments
 //     below); error_text(code) for a positive (runtime) code; kSourceHash.
 // Nothing here launches or touches a buffer: a refused call returns before the backend is reached.
 
 namespace {
+
+// a batch of B envs (max_elems per-step output elements) whose kernels may address it with 32-bit byte offsets:
+// every output offset (<= 32 B/element) and every board record
+bool batch_fits_u32_offsets(int64_t B, int64_t max_elems) {
+  return max_elems <= 0x7FFFFFFF / 32 && (B + 63) / 64 * 64 * (int64_t)tet::kMaxCols * 8 <= 0xFFFFFFFFll;
+}
 
 int fill_step_params(StepParams& p, const TetrisDesc* desc, void* cols, uint64_t* meta, const int32_t* action,
                      int32_t* action_out, const uint8_t* stream, int32_t* cursor, int64_t stream_len, float* obs,
@@ -18,8 +25,7 @@ int fill_step_params(StepParams& p, const TetrisDesc* desc, void* cols, uint64_t
   int rc = tet::check_desc(desc);
   if (rc) return rc;
   if (!cols || !meta || !reward || !done || !lines || !n_valid_next) return TETRIS_E_NULL;
-  if (B <= 0 || max_elems > 0x7FFFFFFF / 32) return TETRIS_E_BATCH;  // every byte offset (<= 32 B/element) fits 32 bits
-  if ((B + 63) / 64 * 64 * (int64_t)tet::kMaxCols * 8 > 0xFFFFFFFFll) return TETRIS_E_BATCH;  // ... and so do the board records
+  if (B <= 0 || !batch_fits_u32_offsets(B, max_elems)) return TETRIS_E_BATCH;
   if (stream && (!cursor || stream_len <= 0)) return TETRIS_E_STREAM;
   p.cols = cols;
   p.meta = meta;
@@ -322,6 +328,41 @@ int TET_ABI(refresh)(const TetrisDesc* desc, const void* cols, uint64_t* meta, u
   p.B = B;
   p.R = desc->num_rows;
   tet::build_table(desc, &p.tab);
+  return backend::launch(desc, p, hip_stream);
+}
+
+// dst env j := src env index[j] (-1: keep); the two batches must not share storage
+int TET_ABI(gather_envs)(const TetrisDesc* desc, const void* src_cols, const uint64_t* src_meta, int64_t B_src,
+                         void* dst_cols, uint64_t* dst_meta, uint8_t* dst_n_valid, uint8_t* dst_piece,
+                         const int32_t* index, uint32_t* status, int64_t B_dst, void* hip_stream) {
+  int rc = tet::check_desc(desc);
+  if (rc) return rc;
+  if (!src_cols || !src_meta || !dst_cols || !dst_meta || !index) return TETRIS_E_NULL;
+  if (B_src <= 0 || B_dst <= 0 || !batch_fits_u32_offsets(B_src, B_src) || !batch_fits_u32_offsets(B_dst, B_dst))
+    return TETRIS_E_BATCH;
+  const int np = tet::n_planes(desc->num_columns, tet::board_packed(desc->word_bytes, desc->num_rows));
+  auto overlap = [](const void* a, int64_t na, const void* b, int64_t nb) {  // byte ranges [a, a + na) and [b, b + nb)
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return x < y + (uintptr_t)nb && y < x + (uintptr_t)na;
+  };
+  if (overlap(src_cols, desc->word_bytes * tet::board_words(B_src, np), dst_cols, desc->word_bytes * tet::board_words(B_dst, np)) ||
+      overlap(src_meta, 8 * B_src, dst_meta, 8 * B_dst))
+    return TETRIS_E_OVERLAP;
+  GatherParams p{};
+  p.src_cols = src_cols;
+  p.src_meta = src_meta;
+  p.dst_cols = dst_cols;
+  p.dst_meta = dst_meta;
+  p.dst_n_valid = dst_n_valid;
+  p.dst_piece = dst_piece;
+  p.index = index;
+  p.status = status;
+  p.B_src = B_src;
+  p.B_dst = B_dst;
+  p.n_planes = np;
+  tet::SetTable tab;
+  tet::build_table(desc, &tab);
+  for (int i = 0; i < desc->n_pieces; ++i) p.fullmask[i] = tab.fullmask[i];
   return backend::launch(desc, p, hip_stream);
 }
 

@@ -154,6 +154,43 @@ TET_HD void refresh_env(const W* cols, uint64_t* meta, uint8_t* n_valid_out, int
   if (n_valid_out) n_valid_out[i] = (uint8_t)popc(mask);
 }
 
+// ---- copy of one env between batches ----------------------------------------------------------------
+// dst env j := src env idx (tetris_hip_gather_envs) on the stored representation: the n_planes words of the
+// board, whatever they pack, and all 64 bits of meta -- mask, piece and bag.  idx == -1 keeps env j; any other
+// idx outside [0, B_src) keeps it too and is reported (returns true).  NP, the plane count, is a template
+// argument so that the loads are one straight run issued before the first store (with NP a launch argument and a
+// guard per plane of an unrolled loop the compiler put a wait on the previous store in front of every store).
+constexpr int kMetaPieces = 16;  // a fullmask entry for every value of meta's 4-bit piece field
+template <typename W, int NP>
+TET_HD bool gather_env(const W* src_cols, const uint64_t* src_meta, int64_t B_src, W* dst_cols, uint64_t* dst_meta,
+                       uint8_t* dst_n_valid, uint8_t* dst_piece, int32_t idx, int64_t j, const uint64_t* fullmask) {
+  if (idx == -1) return false;
+  if (idx < 0 || idx >= B_src) return true;
+  const W* s = src_cols + plane_index(idx, 0, NP);
+  W w[NP];
+#pragma unroll
+  for (int q = 0; q < NP; ++q) w[q] = s[q * kTileEnvs];
+  const uint64_t m = src_meta[idx];
+  W* d = dst_cols + plane_index(j, 0, NP);
+#pragma unroll
+  for (int q = 0; q < NP; ++q) d[q * kTileEnvs] = w[q];
+  dst_meta[j] = m;
+  const int piece = meta_piece(m);
+  if (dst_n_valid) dst_n_valid[j] = (uint8_t)popc(meta_mask(m) & fullmask[piece]);
+  if (dst_piece) dst_piece[j] = (uint8_t)piece;
+  return false;
+}
+// f(IntConst<NP>) for the plane count of a geometry: 4 (five packed columns) to 12 (twelve unpacked)
+template <typename F>
+inline bool gather_variant(int np, F&& f) {
+  switch (np) {
+#define TET_X(N) case N: f(IntConst<N>{}); return true;
+    TET_X(4) TET_X(5) TET_X(6) TET_X(7) TET_X(8) TET_X(9) TET_X(10) TET_X(11) TET_X(12)
+#undef TET_X
+    default: return false;
+  }
+}
+
 // ---- rollout fan-out ------------------------------------------------------------------------------
 // Mean return of the n rollouts of (env i, first action a0); NaN where a0 is not an action of the env.
 // Rollout r has the global id uid (its low word keys the hashes, its high word the key) and reads its
@@ -352,6 +389,21 @@ struct RolloutParams {
   tet::SetTable tab;
 };
 
+struct GatherParams {
+  const void* src_cols;
+  const uint64_t* src_meta;
+  void* dst_cols;
+  uint64_t* dst_meta;
+  uint8_t* dst_n_valid;    // optional
+  uint8_t* dst_piece;      // optional
+  const int32_t* index;    // [B_dst]: src env, -1 = keep
+  uint32_t* status;        // dst's per-wave counters or NULL
+  int64_t B_src;
+  int64_t B_dst;
+  int32_t n_planes;
+  uint64_t fullmask[tet::kMetaPieces];  // of the set's table (tet::SetTable); zero past the last piece
+};
+
 // the blocks travel as kernel arguments (4 KiB at the most), the table inside them
 static_assert(sizeof(StepManyParams) <= 4096 && sizeof(RolloutParams) <= 4096 && sizeof(AfterParams) <= 4096 &&
               sizeof(GreedyParams) <= 4096 && sizeof(ResetParams) <= 4096, "kernel argument block over 4 KiB");
@@ -367,3 +419,28 @@ struct TetrisStepCall {
 constexpr uint64_t kStepCallMagic = 0x5445545249535343ull;  // "TETRISSC"
 
 }  // namespace
+
+#ifndef __HIPCC__
+// The CPU twin of gather_envs_kernel for a host build of this header (the CPU test harness): a loop over dst
+// envs on the shared body, joining the launch overloads of the includer's backend (the unnamed namespaces of
+// one translation unit are one namespace).  hipcc never sees it: the library has no CPU path.
+namespace {
+namespace backend {
+template <typename W>
+inline int gather_envs_host(const GatherParams& p) {
+  const bool known = tet::gather_variant(p.n_planes, [&](auto np) {
+    for (int64_t j = 0; j < p.B_dst; ++j) {
+      const bool invalid = tet::gather_env<W, decltype(np)::value>(static_cast<const W*>(p.src_cols), p.src_meta, p.B_src,
+                                                                  static_cast<W*>(p.dst_cols), p.dst_meta, p.dst_n_valid,
+                                                                  p.dst_piece, p.index[j], j, p.fullmask);
+      if (invalid && p.status) p.status[(j >> 6) * 4 + TETRIS_STATUS_INVALID] += 1;
+    }
+  });
+  return known ? TETRIS_OK : TETRIS_E_COLUMNS;
+}
+inline int launch(const TetrisDesc* desc, const GatherParams& p, void*) {
+  return desc->word_bytes == 4 ? gather_envs_host<uint32_t>(p) : gather_envs_host<uint64_t>(p);
+}
+}  // namespace backend
+}  // namespace
+#endif

@@ -623,6 +623,26 @@ __global__ __launch_bounds__(kRolloutBlock, (after_waves<W, C>(TET_STEP_GREEDY_W
   p.returns[id] = mean;
 }
 
+// dst env j := src env index[j] (tet::gather_env), one lane per dst env, for any column count: the planes are
+// opaque words, NP of them (tet::gather_variant).  The index load (coalesced) is in flight while the twelve fullmask words are staged; the body then
+// issues the gathered plane and meta loads back to back and stores the dst tile record, meta, n_valid and piece
+// coalesced.  Padding lanes take the "keep" path, so nothing past B_dst is written.  Invalid entries go to the
+// wave's own counter slot like the step's: ballot, popcount, a plain read-modify-write by lane 0.
+template <typename W, int NP>
+__global__ __launch_bounds__(kBlock) void gather_envs_kernel(const GatherParams p) {
+  __shared__ uint64_t fullmask[tet::kMetaPieces];
+  const int64_t j = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  const int32_t idx = j < p.B_dst ? p.index[j] : -1;
+  if (threadIdx.x < tet::kMetaPieces) fullmask[threadIdx.x] = p.fullmask[threadIdx.x];
+  __syncthreads();
+  const bool invalid = tet::gather_env<W, NP>(static_cast<const W*>(p.src_cols), p.src_meta, p.B_src, static_cast<W*>(p.dst_cols),
+                                              p.dst_meta, p.dst_n_valid, p.dst_piece, idx, j, fullmask);
+  if (p.status) {
+    const unsigned n_bad = wave_count(invalid);
+    if ((threadIdx.x & 63) == 0 && n_bad) p.status[(j >> 6) * 4 + TETRIS_STATUS_INVALID] += n_bad;
+  }
+}
+
 __global__ void counter_add_kernel(uint64_t* counter, uint64_t n) { *counter += n; }
 
 // done flags -> bitmask (bit i % 8 of byte i / 8): one ballot per wavefront, eight bytes per store.
@@ -851,6 +871,15 @@ int launch(const TetrisDesc* d, const RefreshParams& p, void* s) { return dispat
 int launch(const TetrisDesc* d, const AfterParams& p, void* s) { return dispatch<LaunchAfter>(d, p, (hipStream_t)s); }
 int launch(const TetrisDesc* d, const GreedyParams& p, void* s) { return dispatch<LaunchGreedy>(d, p, (hipStream_t)s); }
 int launch(const TetrisDesc* d, const RolloutParams& p, void* s) { return dispatch<LaunchRollouts>(d, p, (hipStream_t)s); }
+
+int launch(const TetrisDesc* d, const GatherParams& p, void* s) {  // one kernel per word size and plane count, whatever the columns
+  const bool known = tet::gather_variant(p.n_planes, [&](auto np) {
+    constexpr int NP = decltype(np)::value;
+    if (d->word_bytes == 4) hipLaunchKernelGGL((gather_envs_kernel<uint32_t, NP>), grid_for(p.B_dst), dim3(kBlock), 0, (hipStream_t)s, p);
+    else hipLaunchKernelGGL((gather_envs_kernel<uint64_t, NP>), grid_for(p.B_dst), dim3(kBlock), 0, (hipStream_t)s, p);
+  });
+  return known ? (int)hipGetLastError() : TETRIS_E_COLUMNS;
+}
 
 int stream_link(void* from_stream, void* to_stream) {
   // The event releases to DEVICE scope: producer and consumer run on the same GPU (the consumer is the RCCL

@@ -159,6 +159,7 @@ inline const char* error_text(int code) {
     case TETRIS_E_BATCH: return "batch size must be positive";
     case TETRIS_E_STREAM: return "replay stream needs cursor and stream_len > 0";
     case TETRIS_E_STRIDE: return "afterstate strides must be multiples of 4 floats and >= 8";
+    case TETRIS_E_OVERLAP: return "source and destination storage overlap (gather into a second cols / meta pair)";
     default: return nullptr;
   }
 }

@@ -496,6 +496,115 @@ class VecTetris:
                                self.batch_size, self._hip_stream())
         self._lib.check(rc, "tetris_hip_refresh")
 
+    # -- moving envs: fork / resample / reset from a bank -------------------------------------------
+    def _gather_index(self, index, what):
+        """``index`` as a contiguous int32 [batch_size] tensor on the device; an entry no int32 can hold
+        becomes -2 (out of range, reported like any other)."""
+        idx = torch.as_tensor(index, device=self.device)
+        if idx.shape != (self.batch_size,):
+            raise ValueError("%s: index must be [batch_size] = [%d] (got %s)" % (what, self.batch_size, tuple(idx.shape)))
+        if idx.dtype.is_floating_point or idx.dtype.is_complex or idx.dtype == torch.bool:
+            raise ValueError("%s: index must hold integers (got %s)" % (what, idx.dtype))
+        if idx.dtype == torch.int64:
+            idx = torch.where((idx < -1) | (idx > 2**31 - 1), torch.full_like(idx, -2), idx)
+        if idx.dtype != torch.int32 or not idx.is_contiguous():
+            idx = idx.to(torch.int32).contiguous()
+        return idx
+
+    def _gather_call(self, src_cols, src_meta, B_src, dst_cols, dst_meta, idx, status):
+        rc = self._lib.gather_envs(ctypes.byref(self.desc), _ptr(src_cols), _ptr(src_meta), B_src, _ptr(dst_cols),
+                                   _ptr(dst_meta), _ptr(self.n_valid), _ptr(self.piece), _ptr(idx), _ptr(status),
+                                   self.batch_size, self._hip_stream())
+        self._lib.check(rc, "tetris_hip_gather_envs")
+
+    def copy_envs_from(self, src, index):
+        """``self[j] := src[index[j]]`` for every env j: board, current piece, valid mask AND bag, one kernel on
+        the stored words (``tetris_hip_gather_envs``; the batch form of restoring ``current_state`` /
+        ``current_tetromino``, game.py:130-148).  ``src`` is another VecTetris on this device with the same
+        columns, rows and piece set; ``index`` is ``[batch_size]`` ints.  ``-1`` leaves env j as it is; any
+        other entry outside ``[0, src.batch_size)`` leaves it too and is counted, so that :meth:`check` raises
+        IndexError.  ``n_valid`` and ``piece`` are updated; returns ``self``.
+
+        Reset finished envs from a bank of stored states instead of the empty board::
+
+            draws = torch.randint(bank.batch_size, (env.batch_size,), device=env.device)
+            env.copy_envs_from(bank, torch.where(env.done, draws, -1))
+
+        To permute or select within ONE batch use :meth:`gather_`; for a new batch :meth:`fork`."""
+        if not isinstance(src, VecTetris):
+            raise ValueError("copy_envs_from: src must be a VecTetris")
+        if src is self:
+            raise ValueError("copy_envs_from: src is this env; the copy cannot run in place -- use gather_(index)")
+        if (src.num_columns, src.num_rows, list(src.piece_names)) != (self.num_columns, self.num_rows,
+                                                                       list(self.piece_names)):
+            raise ValueError("copy_envs_from: src is %dx%d %s, this env %dx%d %s" % (
+                src.num_columns, src.num_rows, list(src.piece_names), self.num_columns, self.num_rows,
+                list(self.piece_names)))
+        if src.device != self.device:
+            raise ValueError("copy_envs_from: src lives on %s, this env on %s" % (src.device, self.device))
+        if src._stream is not None or self._stream is not None:
+            raise ValueError("copy_envs_from: an env in replay mode (piece_stream / numpy_seeds) cannot take part: "
+                             "its stream columns do not travel")
+        idx = self._gather_index(index, "copy_envs_from")
+        self._gather_call(src.cols, src.meta, src.batch_size, self.cols, self.meta, idx, self.status)
+        return self
+
+    def fork(self, index, env_offset=None, seed=None):
+        """A NEW VecTetris of ``len(index)`` envs, env j a copy of ``self[index[j]]`` (bag included), with this
+        env's geometry, pieces, feature_directions, auto_reset, compute_obs and afterstate_layout; ``seed`` and
+        ``env_offset`` default to this env's and ``step_idx`` is copied, so ``fork(arange(B))`` plays on exactly
+        as this env does.  Every entry must name an env (no ``-1``).
+
+        Replicate one position 4096 times for Monte-Carlo evaluation, or each env K times for a search
+        (another ``env_offset`` makes the copies draw different pieces)::
+
+            mc = env.fork(torch.full((4096,), 17), env_offset=1 << 20)
+            beam = env.fork(torch.arange(env.batch_size).repeat_interleave(K), env_offset=env.batch_size)"""
+        idx = torch.as_tensor(index, device=self.device)
+        if idx.dim() != 1 or idx.numel() == 0:
+            raise ValueError("fork: index must be a non-empty 1-d tensor")
+        if self._stream is not None:
+            raise ValueError("fork: an env in replay mode (piece_stream / numpy_seeds) cannot be forked: its stream "
+                             "columns do not travel")
+        if bool((idx == -1).any()):
+            raise ValueError("fork: every entry of index must name an env of this batch (-1 has nothing to keep)")
+        child = VecTetris(self.num_columns, self.num_rows, idx.numel(), device=self.device, pieces=list(self.piece_names),
+                          auto_reset=self.auto_reset, seed=self.seed if seed is None else seed,
+                          feature_directions=self.feature_directions,
+                          env_offset=self.env_offset if env_offset is None else env_offset,
+                          afterstate_layout=self.afterstate_layout, compute_obs=self.compute_obs)
+        child.step_idx = self.step_idx
+        return child.copy_envs_from(self, idx)
+
+    def gather_(self, index):
+        """In place: ``self[j] := self[index[j]]`` (``-1`` keeps env j; an entry outside the batch keeps it too and
+        is counted, see :meth:`check`).  Resample a population after weighting it, or compact the live envs to
+        the front::
+
+            env.gather_(torch.multinomial(weights, env.batch_size, replacement=True))
+
+        The kernel cannot permute in place, so the envs are gathered into a spare ``cols`` / ``meta`` pair
+        (allocated on first use and kept) which then becomes the env's storage: ``env.cols`` / ``env.meta`` are
+        other tensors afterwards, the bound step call is rebuilt and graphs captured before refuse to replay.
+        Returns ``self``."""
+        if self._stream is not None:
+            raise ValueError("gather_: an env in replay mode (piece_stream / numpy_seeds) cannot be permuted: its "
+                             "stream columns do not travel")
+        idx = self._gather_index(index, "gather_")
+        if getattr(self, "_spare", None) is None:
+            self._spare = (torch.zeros_like(self.cols), torch.zeros_like(self.meta))
+        cols, meta = self._spare
+        own = torch.arange(self.batch_size, dtype=torch.int32, device=self.device)
+        # kept envs travel as index j; an out-of-range entry is counted by the first call (which leaves the
+        # spare's env j alone) and carried over by the second
+        self._gather_call(self.cols, self.meta, self.batch_size, cols, meta, torch.where(idx == -1, own, idx), self.status)
+        bad = (idx < -1) | (idx >= self.batch_size)
+        self._gather_call(self.cols, self.meta, self.batch_size, cols, meta, torch.where(bad, own, torch.full_like(own, -1)), None)
+        self._spare = (self.cols, self.meta)
+        self.cols, self.meta = cols, meta
+        self._invalidate_bound_call()
+        return self
+
     def totals(self):
         """int64 [4] device tensor: (invalid, episodes, lines, steps) summed over the per-wave slots."""
         return (self.status.view(-1, 4).to(torch.int64) & 0xFFFFFFFF).sum(dim=0)
@@ -594,7 +703,7 @@ class StepGraph:
         env = self.env
         if env._generation != self._generation:
             raise RuntimeError("this StepGraph was captured before the env's seed / auto_reset / compute_obs / "
-                               "env_offset changed (or load_state_dict ran): its launches hold the old values -- "
+                               "env_offset changed (or load_state_dict / gather_ ran): its launches hold the old values -- "
                                "capture a new one with env.capture_steps()")
         if env.step_idx != self._expected:  # plain step() calls in between: re-seat the device counter
             self._counter.fill_(env.step_idx)
