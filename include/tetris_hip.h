@@ -192,7 +192,8 @@ int tetris_hip_step_call_run(void* call, const int32_t* action, uint64_t step_id
  * The bound step that also writes the payload of the done/reset gather between GPUs (the
  * path's only exchange) from its own epilogue, so that a gather costs the stepping stream no launch:
  *  done_bits       : uint64[ceil(B / 64)] or NULL: bit l of word w = done flag of env 64 w + l (the bytes
- *                    tetris_hip_pack_done_bits would produce from `done`)
+ *                    tetris_hip_pack_done_bits would produce from `done`); nothing past these ceil(B / 64)
+ *                    words is written, whatever tile of envs the kernel's workgroups cover
  *  status_snapshot : uint32[tetris_hip_status_words(B)] or NULL: the per-wave counter slots as of THIS
  *                    step -- a consistent copy in memory no later step touches (the live `status` slots
  *                    keep moving)

@@ -280,7 +280,9 @@ __global__ __launch_bounds__(BLK, (step_waves<W, CR>())) void step_kernel(const 
       v.w += n_steps;
       if (p.status) st_off(reinterpret_cast<uint4*>(p.status), (i >> 6) * 16u, v);
       if (p.status_snapshot) st_off(reinterpret_cast<uint4*>(p.status_snapshot), (i >> 6) * 16u, v);
-      if (p.done_bits) st_off(p.done_bits, (i >> 6) * 8u, done_mask);
+      // done_bits is uint64[ceil(B / 64)]: a wave of the grid that lies wholly past B has no word there (the
+      // counter buffers are rounded up to the largest tile, tetris_hip_status_words, and take its zero slot)
+      if (p.done_bits && (i & ~63u) < p.B) st_off(p.done_bits, (i >> 6) * 8u, done_mask);
     }
   }
 #if TET_STAMPS
