@@ -271,6 +271,47 @@ int tetris_hip_policy_greedy(const TetrisDesc* desc, const void* cols, const uin
                              float* fitness_all, int64_t B, void* hip_stream);
 
 /*
+ * A POPULATION of linear policies on one batch (the evaluation half of a cross-entropy / CMA-style search over
+ * the weights of game.py:107-120; tetris_hip_gather_envs is the selection half).  Both calls below take
+ *  weights : DEVICE float32[P][8], 16-byte aligned: P weight vectors
+ *  rows    : DEVICE int32[B] or NULL: env i evaluates with weights[rows[i]]; NULL = env i uses row i, which
+ *            needs P >= B (else TETRIS_E_BATCH)
+ * An env whose row is outside [0, P) is left untouched -- no element of any output of that env is written --
+ * and is counted ONCE per launch in status[TETRIS_STATUS_INVALID] of its wave (lazy reporting, as
+ * tetris_hip_gather_envs does for an index out of range).  P < 1, B <= 0 or beyond the bound of
+ * tetris_hip_step: TETRIS_E_BATCH.
+ *
+ * tetris_hip_policy_greedy_rows: tetris_hip_policy_greedy with the weight row taken per env -- the same float32
+ * left-to-right evaluation and the same first-maximum / lowest-index rule, best_action -1 and best_value 0 for
+ * an env without a non-terminal action.  best_value and status may be NULL.  There is no fitness_all.
+ */
+int tetris_hip_policy_greedy_rows(const TetrisDesc* desc, const void* cols, const uint64_t* meta,
+                                  const float* weights, int32_t P, const int32_t* rows, int32_t* best_action,
+                                  float* best_value, uint32_t* status, int64_t B, void* hip_stream);
+
+/*
+ * n_steps greedy steps of every env on its own weight row in ONE launch; boards and meta stay in registers
+ * between the steps.  No auto-reset and no replay stream.  An env that is OVER -- no non-terminal placement
+ * of its current piece, at entry or after one of its steps -- is frozen: it is not stepped, nothing of it is
+ * modified and it is not counted as invalid.  A launch always plays exactly n_steps steps; whether to launch
+ * again is the caller's decision (n_valid below).  Piece draws use tetris_hip_step_many's keys (step k of the
+ * launch is step step_idx0 + k), so while an env is alive its board, meta and lines are bit-identical to
+ * tetris_hip_step_many(policy = 1, auto_reset = 0) with that env's row as `weights`.  Per-env outputs only:
+ *  lines_total / pieces_total : uint32[B], ADDED TO (the caller zeroes them; successive launches accumulate):
+ *                               lines cleared and pieces placed, the last (losing) placement included
+ *  n_valid / piece            : uint8[B] or NULL, written once at the end for every env with a row in range:
+ *                               non-terminal placements of the current piece (0 = the game is over) and the
+ *                               piece's list index
+ *  status                     : per-wave counters or NULL, as tetris_hip_step_many: EPISODES += games that
+ *                               ended in this launch, LINES, STEPS (+ INVALID as above)
+ * n_steps < 1: TETRIS_E_BATCH; cols, meta, weights, lines_total or pieces_total NULL: TETRIS_E_NULL.
+ */
+int tetris_hip_play_linear(const TetrisDesc* desc, void* cols, uint64_t* meta, int32_t n_steps,
+                           const float* weights, int32_t P, const int32_t* rows, uint32_t* lines_total,
+                           uint32_t* pieces_total, uint8_t* n_valid, uint8_t* piece, uint32_t* status,
+                           uint64_t seed, uint64_t step_idx0, int64_t env_offset, int64_t B, void* hip_stream);
+
+/*
  * Tetris.perform_rollouts / single_rollout (game.py:129-160) as a batch fan-out: for every env
  * and every valid first action a, `n` rollouts of `length` steps with the board kept in
  * registers.  returns[i][a] (double[B][a_max]) = mean over the n rollouts of the rollout return

@@ -1,0 +1,67 @@
+"""Greedy play of a population of linear policies on CPU (harness backend): the per-env bodies the kernels run
+(tet::greedy_pick_env, tet::play_step_env), the C-ABI text and the host logic of greedy_actions(rows=) / play."""
+import pytest
+
+import population_cases as pc
+
+FOOT_GEOMETRIES = [(10, 20), (10, 40), (6, 10), (12, 20)]
+
+
+@pytest.mark.parametrize("rows_mode", ["rows", "null"])
+@pytest.mark.parametrize("C,R,pieces", pc.GEOMETRIES)
+def test_pick(host_backend, orc, C, R, pieces, rows_mode):
+    pc.pick("cpu", C, R, pieces, rows_mode, orc if (C, R) == (10, 20) else None)
+
+
+@pytest.mark.parametrize("C,R,pieces", pc.GEOMETRIES)
+def test_play_equals_step_many(host_backend, C, R, pieces):
+    played, frozen = pc.play_equals_step_many("cpu", C, R, pieces)
+    assert played > 0 and ((C, R) != (6, 10) or frozen > 0)
+
+
+def test_play_equals_step_many_negated(host_backend):
+    """games that end inside the launch: the frozen steps are the ones step_many counts as invalid"""
+    played, frozen = pc.play_equals_step_many("cpu", 10, 20, "default", K=40, w=-pc.BCTS)
+    assert played > 0 and frozen > pc.B
+
+
+def test_play_equals_step_many_multi_workgroup(host_backend):
+    pc.play_equals_step_many("cpu", 10, 20, "default", n=pc.B_MULTI, K=8)
+
+
+@pytest.mark.parametrize("C,R", sorted(pc.ORACLE_PLAY))
+def test_play_vs_oracle(host_backend, orc, C, R):
+    pc.play_vs_oracle("cpu", orc, C, R, "default")
+
+
+@pytest.mark.parametrize("C,R,pieces", pc.GEOMETRIES)
+def test_chunks_compose(host_backend, C, R, pieces):
+    pc.chunks_compose("cpu", C, R, pieces)
+
+
+def test_frozen_envs(host_backend):
+    pc.frozen_envs("cpu")
+
+
+@pytest.mark.parametrize("n_steps", [1, 7])
+@pytest.mark.parametrize("C,R,pieces", pc.GEOMETRIES)
+def test_bad_rows(host_backend, C, R, pieces, n_steps):
+    pc.bad_rows("cpu", C, R, pieces, n_steps)
+
+
+@pytest.mark.parametrize("null_arg", pc.GREEDY_ROWS_OPTIONAL)
+@pytest.mark.parametrize("n", pc.FOOTPRINT_BATCHES)
+@pytest.mark.parametrize("C,R", FOOT_GEOMETRIES)
+def test_footprint_greedy_rows(host_backend, C, R, n, null_arg):
+    pc.footprint_greedy_rows("cpu", C, R, n, null_arg)
+
+
+@pytest.mark.parametrize("null_arg", pc.PLAY_OPTIONAL)
+@pytest.mark.parametrize("n", pc.FOOTPRINT_BATCHES)
+@pytest.mark.parametrize("C,R", FOOT_GEOMETRIES)
+def test_footprint_play(host_backend, C, R, n, null_arg):
+    pc.footprint_play("cpu", C, R, n, null_arg)
+
+
+def test_facade(host_backend):
+    pc.facade("cpu")

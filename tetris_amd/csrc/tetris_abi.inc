@@ -3,8 +3,8 @@
 // it for libtetris_hip.so, tests/harness/core_host.cpp for the CPU harness.  The includer defines
 //   TET_ABI(name)       the exported symbol: tetris_hip_##name / tetris_host_##name
 //   namespace backend   what differs between a GPU and a loop over envs, each returning an error code:
-//     launch(const TetrisDesc*, const XParams&, void* stream), overloaded on the eight parameter blocks (the CPU
-//     harness takes GatherParams' from tetris_entry.hpp);
+//     launch(const TetrisDesc*, const XParams&, void* stream), overloaded on the ten parameter blocks (the CPU
+//     harness takes GatherParams', GreedyRowsParams' and PlayParams' from tetris_entry.hpp);
 //     pack_done_bits, counter_add, policy_random, numpy_bag_stream, decode, encode, stream_link (the arguments
 //     below); error_text(code) for a positive (runtime) code; kSourceHash.
 // Nothing here launches or touches a buffer: a refused call returns before the backend is reached.
@@ -285,6 +285,61 @@ int TET_ABI(policy_greedy)(const TetrisDesc* desc, const void* cols, const uint6
   p.R = desc->num_rows;
   p.a_max = desc->a_max;
   for (int i = 0; i < 8; ++i) p.w[i] = weights[i];
+  tet::build_table(desc, &p.tab);
+  return backend::launch(desc, p, hip_stream);
+}
+
+// policy_greedy with the weight row taken per env from a DEVICE matrix weights[P][8]
+int TET_ABI(policy_greedy_rows)(const TetrisDesc* desc, const void* cols, const uint64_t* meta, const float* weights,
+                                int32_t P, const int32_t* rows, int32_t* best_action, float* best_value,
+                                uint32_t* status, int64_t B, void* hip_stream) {
+  int rc = tet::check_desc(desc);
+  if (rc) return rc;
+  if (!cols || !meta || !weights || !best_action) return TETRIS_E_NULL;
+  if (B <= 0 || !batch_fits_u32_offsets(B, B) || P < 1 || (!rows && P < B)) return TETRIS_E_BATCH;
+  GreedyRowsParams p{};
+  p.cols = cols;
+  p.meta = meta;
+  p.weights = weights;
+  p.rows = rows;
+  p.best_action = best_action;
+  p.best_value = best_value;
+  p.status = status;
+  p.B = B;
+  p.P = P;
+  p.R = desc->num_rows;
+  tet::build_table(desc, &p.tab);
+  return backend::launch(desc, p, hip_stream);
+}
+
+// n_steps greedy steps of every env on its own weight row in one launch: no auto-reset, an env that is over is
+// frozen; per-env totals instead of a trajectory
+int TET_ABI(play_linear)(const TetrisDesc* desc, void* cols, uint64_t* meta, int32_t n_steps, const float* weights,
+                         int32_t P, const int32_t* rows, uint32_t* lines_total, uint32_t* pieces_total,
+                         uint8_t* n_valid, uint8_t* piece, uint32_t* status, uint64_t seed, uint64_t step_idx0,
+                         int64_t env_offset, int64_t B, void* hip_stream) {
+  int rc = tet::check_desc(desc);
+  if (rc) return rc;
+  if (!cols || !meta || !weights || !lines_total || !pieces_total) return TETRIS_E_NULL;
+  if (B <= 0 || !batch_fits_u32_offsets(B, B) || n_steps < 1 || P < 1 || (!rows && P < B)) return TETRIS_E_BATCH;
+  PlayParams p{};
+  p.cols = cols;
+  p.meta = meta;
+  p.weights = weights;
+  p.rows = rows;
+  p.lines_total = lines_total;
+  p.pieces_total = pieces_total;
+  p.n_valid = n_valid;
+  p.piece = piece;
+  p.status = status;
+  p.B = (uint32_t)B;
+  p.env_offset = (uint32_t)env_offset;
+  p.P = P;
+  p.n_steps = n_steps;
+  p.seed = seed;
+  p.step_idx0 = step_idx0;
+  tet::fill_step_cfg(p.cfg, desc, 0, false);  // never resets; no observation is written
+  tet::step_keys(seed, step_idx0, p.cfg);
   tet::build_table(desc, &p.tab);
   return backend::launch(desc, p, hip_stream);
 }

@@ -215,6 +215,44 @@ TET_HD double rollout_mean(const W (&col)[C], uint64_t meta, int64_t i, int a0, 
   return mean;
 }
 
+// ---- greedy play of a population of linear policies ---------------------------------------------------
+// (tetris_hip_policy_greedy_rows / tetris_hip_play_linear): env i evaluates with row rows[i] of a DEVICE matrix
+// weights[P][8] (without a row list: row i).  A row outside [0, P) leaves the env alone and is reported.
+TET_HD bool weight_row_ok(int32_t row, int32_t P) { return row >= 0 && row < P; }
+// the eight weights of one row: two 16-byte loads (rows are 32 bytes, the matrix 16-byte aligned); lanes that
+// share a row read the same 32 bytes
+TET_HD void load_weight_row(const float* weights, int32_t row, float (&w)[8]) {
+#if defined(__HIPCC__)
+  const float4* src = reinterpret_cast<const float4*>(weights) + 2 * (int64_t)row;
+  const float4 lo = src[0], hi = src[1];
+  w[0] = lo.x, w[1] = lo.y, w[2] = lo.z, w[3] = lo.w;
+  w[4] = hi.x, w[5] = hi.y, w[6] = hi.z, w[7] = hi.w;
+#else
+  for (int q = 0; q < 8; ++q) w[q] = weights[(int64_t)row * 8 + q];
+#endif
+}
+// the greedy policy's choice for one env (game.py:102-120 on the non-terminal placements): fitness_of on the
+// features of the afterstate walk, GreedyPick's first maximum.  `lut` is an AfterLut.
+template <typename W, int C, int NCH>
+TET_HD GreedyPick greedy_pick_env(const W (&col)[C], uint64_t meta, const SetTable& tab, const uint8_t* lut, int R,
+                                  const float (&w)[8]) {
+  GreedyPick pick;
+  afterstates_env<W, C, NCH>(col, meta, tab, lut, R, [&](bool has, int, int, float (&f)[8], int, int row, bool is_valid) {
+    if (has && is_valid) pick.offer(fitness_of(f, w), row);
+  });
+  return pick;
+}
+// an env is over when its current piece has no non-terminal placement (env_step's n_valid == 0): play freezes it
+TET_HD bool env_over(uint64_t meta) { return popc(meta_mask(meta)) == 0; }
+// one greedy step of an env that is not over: the pick, then the step on the afterstate family's tables
+// (12-row chunks), exactly what step_many's greedy variant runs per step.  SPAD as env_step's.
+template <typename W, int C, int NCH, bool SPAD>
+TET_HD void play_step_env(W (&col)[C], uint64_t& meta, const float (&w)[8], const SetTable& tab, const uint8_t* lut,
+                          W* scratch, int sstride, const StepCfg& cfg, uint32_t env, StepOut& out) {
+  const GreedyPick pick = greedy_pick_env<W, C, NCH>(col, meta, tab, lut, cfg.R, w);
+  env_step<W, C, NCH, 12, true, SPAD>(col, meta, pick.best_row, false, tab, lut, scratch, sstride, cfg, env, -1, -1, out);
+}
+
 // ---- the reference's piece sampler on NumPy's legacy global stream ----------------------------------
 // (tetromino.py:12-22 on top of np.random.seed / np.random.permutation): env i is
 // seeded like `np.random.seed(seeds[i])` right before `game.Tetris(...)` is constructed, and row t of
@@ -389,6 +427,40 @@ struct RolloutParams {
   tet::SetTable tab;
 };
 
+struct GreedyRowsParams {
+  const void* cols;
+  const uint64_t* meta;
+  const float* weights;    // DEVICE [P][8], 16-byte aligned
+  const int32_t* rows;     // [B]: the weight row of each env, or NULL: env i uses row i
+  int32_t* best_action;
+  float* best_value;       // optional
+  uint32_t* status;        // per-wave counters or NULL: an env whose row is outside [0, P) is counted as invalid
+  int64_t B;
+  int32_t P;
+  int32_t R;
+  tet::SetTable tab;
+};
+
+struct PlayParams {
+  void* cols;
+  uint64_t* meta;
+  const float* weights;    // as GreedyRowsParams
+  const int32_t* rows;
+  uint32_t* lines_total;   // [B], added to
+  uint32_t* pieces_total;  // [B], added to
+  uint8_t* n_valid;        // optional, written once at the end
+  uint8_t* piece;          // optional
+  uint32_t* status;        // optional
+  uint32_t B;
+  uint32_t env_offset;     // global env index of env 0 (mod 2^32)
+  int32_t P;
+  int32_t n_steps;
+  uint64_t seed;
+  uint64_t step_idx0;
+  tet::StepCfg cfg;        // (the keys are derived per step from seed and step_idx0)
+  tet::SetTable tab;
+};
+
 struct GatherParams {
   const void* src_cols;
   const uint64_t* src_meta;
@@ -406,7 +478,8 @@ struct GatherParams {
 
 // the blocks travel as kernel arguments (4 KiB at the most), the table inside them
 static_assert(sizeof(StepManyParams) <= 4096 && sizeof(RolloutParams) <= 4096 && sizeof(AfterParams) <= 4096 &&
-              sizeof(GreedyParams) <= 4096 && sizeof(ResetParams) <= 4096, "kernel argument block over 4 KiB");
+              sizeof(GreedyParams) <= 4096 && sizeof(ResetParams) <= 4096 && sizeof(GreedyRowsParams) <= 4096 &&
+              sizeof(PlayParams) <= 4096, "kernel argument block over 4 KiB");
 
 // bound step call: everything that does not change between steps is prepared once
 struct TetrisStepCall {
@@ -440,6 +513,97 @@ inline int gather_envs_host(const GatherParams& p) {
 }
 inline int launch(const TetrisDesc* desc, const GatherParams& p, void*) {
   return desc->word_bytes == 4 ? gather_envs_host<uint32_t>(p) : gather_envs_host<uint64_t>(p);
+}
+
+// The CPU twins of greedy_rows_kernel and play_linear_kernel: loops over envs on the shared bodies
+// (tet::greedy_pick_env, tet::play_step_env), on the instantiation the library launches for the geometry.
+// f(W{}, IntConst<C>, IntConst<NCH>, BoolConst<PACK>)
+template <typename F>
+inline int host_variant(const TetrisDesc* desc, F&& f) {
+  switch (desc->num_columns) {
+#define TET_X(CC)                                                                                                  \
+  case CC:                                                                                                         \
+    if (desc->word_bytes == 4)                                                                                     \
+      tet::kernel_variant<uint32_t>(desc->num_rows, [&](auto nch, auto, auto pack) { f(uint32_t{}, tet::IntConst<CC>{}, nch, pack); }); \
+    else                                                                                                           \
+      tet::kernel_variant<uint64_t>(desc->num_rows, [&](auto nch, auto, auto pack) { f(uint64_t{}, tet::IntConst<CC>{}, nch, pack); }); \
+    return TETRIS_OK;
+    TET_COLUMNS(TET_X)
+#undef TET_X
+    default:
+      return TETRIS_E_COLUMNS;
+  }
+}
+
+template <typename W, int C, int NCH, bool PACK>
+inline void greedy_rows_host(const GreedyRowsParams& p) {
+  for (int64_t i = 0; i < p.B; ++i) {
+    const int32_t row = p.rows ? p.rows[i] : (int32_t)i;
+    if (!tet::weight_row_ok(row, p.P)) {  // untouched, counted
+      if (p.status) p.status[(i >> 6) * 4 + TETRIS_STATUS_INVALID] += 1;
+      continue;
+    }
+    float w[8];
+    tet::load_weight_row(p.weights, row, w);
+    W col[C];
+    tet::load_board<W, C, PACK>(static_cast<const W*>(p.cols), p.B, i, col);
+    const tet::GreedyPick pick = tet::greedy_pick_env<W, C, NCH>(col, p.meta[i], p.tab, kAfterLut.bytes, p.R, w);
+    p.best_action[i] = pick.best_row;
+    if (p.best_value) p.best_value[i] = pick.best;
+  }
+}
+inline int launch(const TetrisDesc* desc, const GreedyRowsParams& p, void*) {
+  return host_variant(desc, [&](auto w, auto c, auto nch, auto pack) {
+    greedy_rows_host<decltype(w), decltype(c)::value, decltype(nch)::value, decltype(pack)::value>(p);
+  });
+}
+
+template <typename W, int C, int NCH, bool PACK>
+inline void play_linear_host(const PlayParams& p) {
+  W* cols = static_cast<W*>(p.cols);
+  const int64_t B = p.B;
+  tet::StepCfg cfg = p.cfg;
+  for (int64_t i = 0; i < B; ++i) {
+    uint32_t* slot = p.status ? p.status + (i >> 6) * 4 : nullptr;
+    const int32_t row = p.rows ? p.rows[i] : (int32_t)i;
+    if (!tet::weight_row_ok(row, p.P)) {  // untouched, counted once per launch
+      if (slot) slot[TETRIS_STATUS_INVALID] += 1;
+      continue;
+    }
+    float w[8];
+    tet::load_weight_row(p.weights, row, w);
+    W col[C], scratch[C];
+    tet::load_board<W, C, PACK>(cols, B, i, col);
+    uint64_t m = p.meta[i];
+    uint32_t lines = 0, pieces = 0;
+    for (int k = 0; k < p.n_steps; ++k) {
+      if (tet::env_over(m)) continue;  // frozen
+      tet::step_keys(p.seed, p.step_idx0 + (uint64_t)k, cfg);
+      tet::StepOut out;
+      tet::play_step_env<W, C, NCH, false>(col, m, w, p.tab, kAfterLut.bytes, scratch, 1, cfg, p.env_offset + (uint32_t)i, out);
+      if (out.invalid) continue;
+      lines += (uint32_t)out.lines;
+      pieces += 1;
+      if (slot) {
+        slot[TETRIS_STATUS_EPISODES] += out.done;
+        slot[TETRIS_STATUS_LINES] += out.lines;
+        slot[TETRIS_STATUS_STEPS] += 1;
+      }
+    }
+    if (pieces) {
+      tet::store_board<W, C, PACK>(cols, B, i, col);
+      p.meta[i] = m;
+      p.lines_total[i] += lines;
+      p.pieces_total[i] += pieces;
+    }
+    if (p.n_valid) p.n_valid[i] = (uint8_t)tet::popc(tet::meta_mask(m));
+    if (p.piece) p.piece[i] = (uint8_t)tet::meta_piece(m);
+  }
+}
+inline int launch(const TetrisDesc* desc, const PlayParams& p, void*) {
+  return host_variant(desc, [&](auto w, auto c, auto nch, auto pack) {
+    play_linear_host<decltype(w), decltype(c)::value, decltype(nch)::value, decltype(pack)::value>(p);
+  });
 }
 }  // namespace backend
 }  // namespace

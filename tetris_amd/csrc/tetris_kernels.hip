@@ -315,6 +315,11 @@ __global__ __launch_bounds__(BLK, (step_waves<W, CR>())) void step_kernel(const 
 #ifndef TET_AFTER_WAVES64
 #define TET_AFTER_WAVES64 2
 #endif
+// play_linear_kernel: 0 keeps a lane's eight weights in registers across the step loop, 1 reloads the row in
+// every step (an L2 hit).  DESIGN.md section 3.5 has the register and scratch report of both forms.
+#ifndef TET_PLAY_RELOAD_W
+#define TET_PLAY_RELOAD_W 0
+#endif
 // A hardware hazard met on the way (round 3): on gfx950 a 64-bit shift -- v_lshlrev_b64, v_lshrrev_b64,
 // v_ashrrev_i64 -- whose 32-bit shift amount sits in the LAST vector register of the wave's allocation (v255
 // of 256, v167 of 168, v127 of 128) shifts by (v0 & 63) instead whenever another wave shares the SIMD
@@ -586,6 +591,121 @@ __global__ __launch_bounds__(kBlock, (after_waves<W, C>(TET_GREEDY_WAVES))) void
   if (p.best_value) p.best_value[i] = pick.best;
 }
 
+// greedy_kernel with the weight row taken per env from a device matrix (tet::load_weight_row: two 16-byte loads
+// per lane, issued with the board's).  An env whose row is outside [0, P) writes nothing and goes to its wave's
+// counter slot like gather_envs_kernel's bad entries.  No lane leaves early: the ballot sees the whole wave.
+template <typename W, int C, int NCH>
+__global__ __launch_bounds__(kBlock, (after_waves<W, C>(TET_GREEDY_WAVES))) void greedy_rows_kernel(const GreedyRowsParams p) {
+  __shared__ SetTable tab;
+  __shared__ __attribute__((aligned(16))) uint8_t hole_lut[tet::kAfterLutBytes];
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  const bool live = i < p.B;
+  const int32_t row = !live ? -1 : (p.rows ? p.rows[i] : (int32_t)i);
+  const bool ok = live && tet::weight_row_ok(row, p.P);
+  float w[8];
+  tet::load_weight_row(p.weights, ok ? row : 0, w);
+  stage_after_lut(hole_lut);
+  stage_table(tab, p.tab);
+  if (ok) {
+    W col[C];
+    tet::load_board<W, C, (NCH != 0 && !TET_NO_PACK)>(static_cast<const W*>(p.cols), p.B, i, col);
+    const tet::GreedyPick pick = tet::greedy_pick_env<W, C, NCH>(col, p.meta[i], tab, hole_lut, p.R, w);
+    p.best_action[i] = pick.best_row;
+    if (p.best_value) p.best_value[i] = pick.best;
+  }
+  if (p.status) {
+    const unsigned n_bad = wave_count(live && !ok);
+    if ((threadIdx.x & 63) == 0 && n_bad) p.status[(i >> 6) * 4 + TETRIS_STATUS_INVALID] += n_bad;
+  }
+}
+
+// n_steps greedy steps of every env on ITS weight row in one launch (tetris_hip_play_linear): step_many_kernel's
+// greedy variant without the trajectory -- board and meta in registers between the steps, per-env totals at the
+// end -- and without auto-reset: a lane whose env is over skips the body for the rest of the launch.  The trip
+// count is n_steps whatever the games do; the wave counters stay outside the divergent body.  The eight weights
+// are loaded once in front of the loop and stay in registers (DESIGN.md section 3.5 has the register report).
+template <typename W, int C, int NCH>
+__global__ __launch_bounds__(step_block<W>(), (after_waves<W, C>(TET_STEP_GREEDY_WAVES))) void play_linear_kernel(const PlayParams p) {
+  constexpr int kBlock = step_block<W>();  // shadows the file-wide tile size inside this kernel
+  __shared__ StepLds<W, C, kBlock, 12, true> lds;
+  SetTable& tab = lds.tab;
+  uint8_t* const hole_lut = lds.lut;
+  auto& lane_cols = lds.lane_cols;
+  constexpr bool SPAD = tet::scratch_padded<W, C, NCH, 12, true>();
+  static_assert(sizeof(lds.lane_cols) / sizeof(lds.lane_cols[0]) >= (SPAD ? C + 3 : C), "the unclamped stamp needs its three columns");
+  const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+  const bool live = i < p.B;
+  const uint32_t ii = live ? i : 0;
+  const bool wave_live = (i & ~63u) < p.B;  // (wave-uniform) this wave holds envs: it has a counter slot to keep
+  constexpr bool PACK = NCH != 0 && !TET_NO_PACK;
+  constexpr int NP = tet::n_planes(C, PACK);
+  // every global load of the lane first: board, meta, its row index and weights, the wave's counters
+  const uint32_t rec = record_off<W, NP>(ii);
+  W col[C];
+  {
+    W pl[NP];
+#pragma unroll
+    for (int q = 0; q < NP; ++q) pl[q] = ld_off(static_cast<const W*>(p.cols), rec + (uint32_t)(q * 64 * sizeof(W)));
+    tet::unpack_board<W, C, PACK>(pl, col);
+  }
+  uint64_t meta = ld_off(p.meta, ii * 8u);
+  const int32_t row = p.rows ? ld_off(p.rows, ii * 4u) : (int32_t)ii;
+  const bool ok = live && tet::weight_row_ok(row, p.P);
+  float w[8];
+  if (!TET_PLAY_RELOAD_W) tet::load_weight_row(p.weights, ok ? row : 0, w);
+  uint4 slot = make_uint4(0, 0, 0, 0);
+  if (p.status && wave_live) slot = ld_off(reinterpret_cast<const uint4*>(p.status), (i >> 6) * 16u);
+  stage_after_lut(hole_lut);
+  stage_table(tab, p.tab);
+  unsigned n_done = 0, n_lines = 0, n_steps = 0;
+  uint32_t my_lines = 0, my_pieces = 0;
+  tet::StepCfg cfg = p.cfg;
+#pragma unroll 1
+  for (int k = 0; k < p.n_steps; ++k) {
+    cfg.key_step = tet::hash_key(p.seed, (p.step_idx0 + (uint64_t)k) * 4u + 0u);  // (== tet::step_keys)
+    cfg.key_policy = tet::hash_key(p.seed, (p.step_idx0 + (uint64_t)k) * 4u + 3u);
+    bool stepped = false, done = false;
+    int lines = 0;
+    if (ok && !tet::env_over(meta)) {
+      if (TET_PLAY_RELOAD_W) tet::load_weight_row(p.weights, row, w);
+      tet::StepOut out;
+      tet::play_step_env<W, C, NCH, SPAD>(col, meta, w, tab, hole_lut, &lane_cols[0][threadIdx.x], kBlock, cfg,
+                                          p.env_offset + i, out);
+      if (!out.invalid) {
+        stepped = true;
+        done = out.done != 0;
+        lines = out.lines;
+        my_lines += (uint32_t)out.lines;
+        my_pieces += 1;
+      }
+    }
+    n_done += wave_count(done);
+    n_lines += wave_sum(3, lines);
+    n_steps += wave_count(stepped);
+  }
+  if (my_pieces) {  // an env that was over at entry keeps every byte
+    W pl[NP];
+    tet::pack_board<W, C, PACK>(col, pl);
+#pragma unroll
+    for (int q = 0; q < NP; ++q) st_off(static_cast<W*>(p.cols), rec + (uint32_t)(q * 64 * sizeof(W)), pl[q]);
+    st_off(p.meta, i * 8u, meta);
+    st_off(p.lines_total, i * 4u, ld_off(p.lines_total, i * 4u) + my_lines);
+    st_off(p.pieces_total, i * 4u, ld_off(p.pieces_total, i * 4u) + my_pieces);
+  }
+  if (ok) {
+    if (p.n_valid) st_off(p.n_valid, i, (uint8_t)tet::popc(tet::meta_mask(meta)));
+    if (p.piece) st_off(p.piece, i, (uint8_t)tet::meta_piece(meta));
+  }
+  const unsigned n_inv = wave_count(live && !ok);
+  if (p.status && wave_live && (threadIdx.x & 63) == 0) {
+    slot.x += n_inv;
+    slot.y += n_done;
+    slot.z += n_lines;
+    slot.w += n_steps;
+    st_off(reinterpret_cast<uint4*>(p.status), (i >> 6) * 16u, slot);
+  }
+}
+
 // Tetris.perform_rollouts (game.py:150-160) as a fan-out: one lane per (env, first action) runs its
 // n rollouts back to back with the board in registers; nothing but the mean returns is written.
 // 512 lanes per workgroup: with the 35 KiB of afterstate tables two workgroups = 16 waves fit a CU
@@ -782,6 +902,22 @@ struct LaunchGreedy {
   }
 };
 template <typename W, int C>
+struct LaunchGreedyRows {
+  static void run(const GreedyRowsParams& p, hipStream_t s) {
+    tet::kernel_variant<W>(p.R, [&](auto nch, auto, auto) {
+      hipLaunchKernelGGL((greedy_rows_kernel<W, C, decltype(nch)::value>), grid_for(p.B), dim3(kBlock), 0, s, p);
+    });
+  }
+};
+template <typename W, int C>
+struct LaunchPlay {
+  static void run(const PlayParams& p, hipStream_t s) {
+    tet::kernel_variant<W>(p.cfg.R, [&](auto nch, auto, auto) {
+      hipLaunchKernelGGL((play_linear_kernel<W, C, decltype(nch)::value>), step_grid<W>(p.B), dim3(step_block<W>()), 0, s, p);
+    });
+  }
+};
+template <typename W, int C>
 struct LaunchAfter {
   static void run(const AfterParams& p, hipStream_t s) {
     tet::kernel_variant<W>(p.R, [&](auto nch, auto, auto) {
@@ -798,6 +934,8 @@ template <> struct LaunchId<LaunchRefresh> { static constexpr int value = 3; };
 template <> struct LaunchId<LaunchRollouts> { static constexpr int value = 4; };
 template <> struct LaunchId<LaunchGreedy> { static constexpr int value = 5; };
 template <> struct LaunchId<LaunchAfter> { static constexpr int value = 6; };
+template <> struct LaunchId<LaunchGreedyRows> { static constexpr int value = 7; };
+template <> struct LaunchId<LaunchPlay> { static constexpr int value = 8; };
 
 template <template <typename, int> class Launcher, int CC, typename P>
 inline void launch_words(int word_bytes, const void* p, hipStream_t s) {
@@ -815,6 +953,8 @@ int launch_part(int which, int word_bytes, const void* p, hipStream_t s) {
     case 4: launch_words<LaunchRollouts, CC, RolloutParams>(word_bytes, p, s); break;
     case 5: launch_words<LaunchGreedy, CC, GreedyParams>(word_bytes, p, s); break;
     case 6: launch_words<LaunchAfter, CC, AfterParams>(word_bytes, p, s); break;
+    case 7: launch_words<LaunchGreedyRows, CC, GreedyRowsParams>(word_bytes, p, s); break;
+    case 8: launch_words<LaunchPlay, CC, PlayParams>(word_bytes, p, s); break;
     default: return TETRIS_E_DESC;
   }
   return (int)hipGetLastError();
@@ -873,6 +1013,8 @@ int launch(const TetrisDesc* d, const RefreshParams& p, void* s) { return dispat
 int launch(const TetrisDesc* d, const AfterParams& p, void* s) { return dispatch<LaunchAfter>(d, p, (hipStream_t)s); }
 int launch(const TetrisDesc* d, const GreedyParams& p, void* s) { return dispatch<LaunchGreedy>(d, p, (hipStream_t)s); }
 int launch(const TetrisDesc* d, const RolloutParams& p, void* s) { return dispatch<LaunchRollouts>(d, p, (hipStream_t)s); }
+int launch(const TetrisDesc* d, const GreedyRowsParams& p, void* s) { return dispatch<LaunchGreedyRows>(d, p, (hipStream_t)s); }
+int launch(const TetrisDesc* d, const PlayParams& p, void* s) { return dispatch<LaunchPlay>(d, p, (hipStream_t)s); }
 
 int launch(const TetrisDesc* d, const GatherParams& p, void* s) {  // one kernel per word size and plane count, whatever the columns
   const bool known = tet::gather_variant(p.n_planes, [&](auto np) {

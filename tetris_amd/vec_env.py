@@ -355,12 +355,50 @@ class VecTetris:
 
     BCTS_WEIGHTS = (-24.04, -19.77, -13.08, -12.63, -10.49, -9.22, 6.6, -1.61)  # game.py:111-118
 
-    def greedy_actions(self, weights=None, include_fitness=False):
+    def _population(self, weights, rows, what):
+        """(weights float32 [P, 8] contiguous on the device, rows int32 [B] or None) for the per-env-row calls"""
+        if not isinstance(weights, torch.Tensor) or weights.dim() != 2 or weights.shape[1] != 8:
+            raise ValueError("%s: weights must be a [P, 8] tensor" % what)
+        if weights.device != self.device:
+            raise ValueError("%s: weights live on %s, this env on %s" % (what, weights.device, self.device))
+        if weights.dtype != torch.float32 or not weights.is_contiguous():
+            weights = weights.to(torch.float32).contiguous()
+        if weights.shape[0] < 1 or weights.data_ptr() % 16:
+            raise ValueError("%s: weights need at least one row and 16-byte alignment" % what)
+        if rows is None:
+            if weights.shape[0] < self.batch_size:
+                raise ValueError("%s: without rows env i uses row i: weights must have at least batch_size = %d rows "
+                                 "(got %d)" % (what, self.batch_size, weights.shape[0]))
+            return weights, None
+        return weights, self._gather_index(rows, what)
+
+    def greedy_actions(self, weights=None, include_fitness=False, rows=None):
         """Tetris.get_best_policy / fitness (game.py:102-120) for every env, without materialising
         the feature matrix: returns ``(best_action int32 [B], best_value float32 [B])`` -- the first
         non-terminal action of maximal linear fitness (-1 when the env has none) -- and with
         ``include_fitness`` also ``fitness_all float32 [B, a_max]`` over ALL placements in raw order
-        (terminal included, the domain of the reference's policy vector)."""
+        (terminal included, the domain of the reference's policy vector).
+
+        A population: ``weights`` as a 2-D tensor ``[P, 8]`` on the env's device and ``rows`` ``[B]`` ints (or
+        ``None``: env i uses row i) evaluates every env with ITS row (``tetris_hip_policy_greedy_rows``; no
+        ``include_fitness``).  A row outside ``[0, P)`` leaves that env's entries as they were and is counted,
+        see :meth:`check`."""
+        if isinstance(weights, torch.Tensor) and weights.dim() == 2:
+            if include_fitness:
+                raise ValueError("greedy_actions: include_fitness is not available with per-env weight rows")
+            wt, idx = self._population(weights, rows, "greedy_actions")
+            B = self.batch_size
+            if not hasattr(self, "_best_action"):
+                self._best_action = torch.empty(B, dtype=torch.int32, device=self.device)
+                self._best_value = torch.empty(B, dtype=torch.float32, device=self.device)
+                self._fitness_all = None
+            rc = self._lib.policy_greedy_rows(ctypes.byref(self.desc), _ptr(self.cols), _ptr(self.meta), _ptr(wt),
+                                              wt.shape[0], _ptr(idx), _ptr(self._best_action), _ptr(self._best_value),
+                                              _ptr(self.status), B, self._hip_stream())
+            self._lib.check(rc, "tetris_hip_policy_greedy_rows")
+            return self._best_action, self._best_value
+        if rows is not None:
+            raise ValueError("greedy_actions: rows needs weights as a [P, 8] tensor")
         w = (ctypes.c_float * 8)(*(self.BCTS_WEIGHTS if weights is None else [float(x) for x in weights]))
         B = self.batch_size
         if not hasattr(self, "_best_action"):
@@ -379,6 +417,47 @@ class VecTetris:
         if include_fitness:
             return self._best_action, self._best_value, fa
         return self._best_action, self._best_value
+
+    def play(self, weights, rows=None, max_steps=1 << 20, chunk=64):
+        """Greedy play of a population of linear policies: env i plays the greedy policy on row ``rows[i]`` of
+        ``weights`` (a ``[P, 8]`` tensor on the env's device; ``rows=None``: env i uses row i) until its game is
+        over or ``max_steps`` steps have been played -- the evaluation half of a cross-entropy / CMA-style search
+        over the weights, :meth:`gather_` / :meth:`fork` being the selection half.
+
+        The steps run in launches of ``chunk`` steps (``tetris_hip_play_linear``: boards in registers, nothing
+        but per-env totals written); after each launch one ``n_valid.any()`` read-back -- the only
+        synchronisation -- decides whether to launch again.  Returns ``dict(lines uint32 [B], pieces uint32 [B],
+        done bool [B])``: lines cleared and pieces placed by each env in THIS call (the losing placement
+        included), and whether its game is over.
+
+        ``play`` never resets an env, whatever ``auto_reset`` says: a finished env stays as it ended (reset it
+        with :meth:`reset` or refill it with :meth:`copy_envs_from`).  An env that is already over is left
+        alone.  ``step_idx`` advances by the steps launched and ``n_valid`` / ``piece`` describe the boards
+        afterwards, so ``step()`` continues the surviving envs; like ``step_many`` it leaves earlier
+        ``get_after_states()`` results describing the boards as they were.  A row outside ``[0, P)`` leaves its
+        env untouched and is counted once per launch, see :meth:`check`.  Replay mode is refused."""
+        if self._stream is not None:
+            raise ValueError("play draws pieces from the device bag (no replay stream)")
+        max_steps, chunk = int(max_steps), int(chunk)
+        if max_steps < 0 or chunk < 1:
+            raise ValueError("play: max_steps must be >= 0 and chunk >= 1")
+        wt, idx = self._population(weights, rows, "play")
+        B, dev = self.batch_size, self.device
+        lines = torch.zeros(B, dtype=torch.int32, device=dev)
+        pieces = torch.zeros(B, dtype=torch.int32, device=dev)
+        played = 0
+        while played < max_steps:
+            k = min(chunk, max_steps - played)
+            rc = self._lib.play_linear(ctypes.byref(self.desc), _ptr(self.cols), _ptr(self.meta), k, _ptr(wt),
+                                       wt.shape[0], _ptr(idx), _ptr(lines), _ptr(pieces), _ptr(self.n_valid),
+                                       _ptr(self.piece), _ptr(self.status), self.seed, self.step_idx,
+                                       self.env_offset, B, self._hip_stream())
+            self._lib.check(rc, "tetris_hip_play_linear")
+            self.step_idx += k
+            played += k
+            if not bool(self.n_valid.any()):
+                break
+        return dict(lines=lines.view(torch.uint32), pieces=pieces.view(torch.uint32), done=self.n_valid == 0)
 
     def rollouts(self, length=5, n=5, policy="random", weights=None, pieces=None):
         """Tetris.perform_rollouts (game.py:150-160) for every env and every valid first action:
