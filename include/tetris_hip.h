@@ -65,7 +65,9 @@ enum {
   TETRIS_E_BATCH = -6,       /* B <= 0 (tetris_hip_step: or B beyond ~53 M envs per call: 32-bit byte offsets) */
   TETRIS_E_STREAM = -7,      /* replay stream given without cursor / length */
   TETRIS_E_STRIDE = -8,      /* afterstate strides not multiples of 4 floats / too small / matrix beyond 2^32 float4 */
-  TETRIS_E_OVERLAP = -9      /* tetris_hip_gather_envs: source and destination storage overlap */
+  TETRIS_E_OVERLAP = -9,     /* tetris_hip_gather_envs: source and destination storage overlap */
+  TETRIS_E_ALIGN = -10,      /* softmax calls: weights / score / score_total not 16-byte aligned */
+  TETRIS_E_TEMPERATURE = -11 /* softmax calls: temperature (or 1 / temperature) not positive and finite */
 };
 
 /* Constructor arguments of game.Tetris (game.py:21-23) that shape the kernels. */
@@ -310,6 +312,75 @@ int tetris_hip_play_linear(const TetrisDesc* desc, void* cols, uint64_t* meta, i
                            const float* weights, int32_t P, const int32_t* rows, uint32_t* lines_total,
                            uint32_t* pieces_total, uint8_t* n_valid, uint8_t* piece, uint32_t* status,
                            uint64_t seed, uint64_t step_idx0, int64_t env_offset, int64_t B, void* hip_stream);
+
+/*
+ * The SOFTMAX linear policy of the reference's utils.py:26-38 (compute_action_probabilities,
+ * grad_of_log_action_probabilities) in the kernel: a sampled action per env with its log-probability and the
+ * gradient of that log-probability, without the [B][a_max][8] feature matrix ever reaching memory (the learning
+ * half of the population calls above; weights / P / rows and the contract of a row outside [0, P) are theirs).
+ * For the non-terminal placement k of an env (k = the action, features f as tetris_hip_afterstates writes them --
+ * direct_by applied when the descriptor has it; the greedy calls evaluate undirected features):
+ *   logit  u_k = (sum_q f[q] * w[q], float32, left to right) * inv_t,  inv_t = 1.0f / temperature in float32;
+ *          reproducible bit for bit in NumPy float32
+ *   p_k    = exp(u_k - logz),  logz = log sum_k exp(u_k): an online log-sum-exp in float32 -- running maximum m,
+ *          s = sum exp(u_k - m), g[q] = sum exp(u_k - m) f_k[q], s and g rescaled when m grows -- accumulated IN
+ *          THE ORDER THE PLACEMENT WALK EMITS: the placements that complete a row come after all the others, not
+ *          in row order.  The sums are reproducible for a board but not independent of that order.
+ *   draw   Gumbel-max, counter-based: the action is the row of maximal z_k = u_k - log(-log(U_k)), of exactly
+ *          equal z the lower row, with
+ *            U_k = ((h_k >> 8) + 1) * 2^-24                                        in (0, 1]
+ *            h_k = hash_env(mix32(key ^ ((uint32_t)(k + 1) * 0x9E3779B1u)), env)
+ *            key = hash_key(seed, 4 * step_idx + 1),  env = (env_offset + i) mod 2^32
+ *            mix32(x):       x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16
+ *            hash_env(k, e): h = (k ^ e) * 0x9E3779B1; h ^= h >> 16; h *= 0x85EBCA6B; h ^= h >> 13
+ *            hash_key(s, c): k = mix32((uint32_t)s ^ 0x9E3779B9); k = mix32(k ^ (uint32_t)(s >> 32));
+ *                            k = mix32(k ^ (uint32_t)c); k = mix32(k ^ (uint32_t)(c >> 32))
+ *          (all in uint32 arithmetic; log and exp are float32).  The draw depends on (seed, step_idx, env) only:
+ *          the same call repeated returns the same actions, and shards with their env_offset those of the whole.
+ *   logp   = u_a - logz at the drawn action a, evaluated as (u_a - m) - log(s) so that logits in the thousands do
+ *          not cancel it away
+ *   score  [q] = f_a[q] - sum_k p_k f_k[q]  (= g[q] / s): grad_of_log_action_probabilities, the gradient of logp
+ *          with respect to the weights WITHOUT the factor 1 / temperature -- as upstream, which omits it too.
+ * An env without a non-terminal placement: action -1, logp = logz = 0, score = 0 (logits all -inf).  An env with
+ * exactly one: logp = 0 and score = 0 exactly.  Weights and temperature must keep every logit finite.
+ * temperature (or 1.0f / temperature) not positive and finite: TETRIS_E_TEMPERATURE; weights, score or score_total
+ * not 16-byte aligned: TETRIS_E_ALIGN; nothing is launched.
+ *
+ * tetris_hip_policy_softmax_rows: one decision per env, boards untouched.
+ *  action  : int32[B]                       logp   : float32[B]
+ *  score   : float32[B][8] or NULL          logz   : float32[B] or NULL
+ *  logits  : float32[B][a_max] or NULL: entry k = u_k for k < n_valid, -inf beyond
+ *  status  : per-wave counters or NULL (INVALID += envs whose row is outside [0, P); nothing of them is written)
+ * Play the draw with tetris_hip_step(action, step_idx): the sampling key uses a counter of that step no other
+ * call uses.
+ */
+int tetris_hip_policy_softmax_rows(const TetrisDesc* desc, const void* cols, const uint64_t* meta,
+                                   const float* weights, int32_t P, const int32_t* rows, float temperature,
+                                   int32_t* action, float* logp, float* score, float* logz, float* logits,
+                                   uint32_t* status, uint64_t seed, uint64_t step_idx, int64_t env_offset,
+                                   int64_t B, void* hip_stream);
+
+/*
+ * n_steps SAMPLED steps of every env in ONE launch: tetris_hip_play_linear with the pick drawn as above -- boards
+ * and meta in registers, no auto-reset, no replay stream, an env that is over is frozen and not counted invalid,
+ * always n_steps steps.  Step k of the launch is step step_idx0 + k, for the sampling key and for the piece
+ * draws: while an env is alive its board, meta, lines and the sums below are bit-identical to n_steps rounds of
+ * tetris_hip_policy_softmax_rows(step_idx0 + k) followed by tetris_hip_step(action, step_idx0 + k).
+ * Per-env totals, all ADDED TO by the env's lane and only when it placed a piece:
+ *  lines_total / pieces_total : uint32[B], as tetris_hip_play_linear
+ *  logp_total                 : float32[B] or NULL: sum of logp over the pieces the env placed
+ *  score_total                : float32[B][8], 16-byte aligned: sum of score over those pieces
+ *    both start from the value in memory and take one float32 addition per piece in step order, so successive
+ *    launches compose bit for bit.  Episodic REINFORCE needs no more:
+ *    grad J ~ sum_env (return_env - baseline) * score_total_env
+ *  n_valid / piece / status   : as tetris_hip_play_linear
+ * n_steps < 1: TETRIS_E_BATCH; cols, meta, weights, lines_total, pieces_total or score_total NULL: TETRIS_E_NULL.
+ */
+int tetris_hip_play_softmax(const TetrisDesc* desc, void* cols, uint64_t* meta, int32_t n_steps,
+                            const float* weights, int32_t P, const int32_t* rows, float temperature,
+                            uint32_t* lines_total, uint32_t* pieces_total, float* logp_total, float* score_total,
+                            uint8_t* n_valid, uint8_t* piece, uint32_t* status, uint64_t seed, uint64_t step_idx0,
+                            int64_t env_offset, int64_t B, void* hip_stream);
 
 /*
  * Tetris.perform_rollouts / single_rollout (game.py:129-160) as a batch fan-out: for every env

@@ -17,6 +17,9 @@ bool batch_fits_u32_offsets(int64_t B, int64_t max_elems) {
   return max_elems <= 0x7FFFFFFF / 32 && (B + 63) / 64 * 64 * (int64_t)tet::kMaxCols * 8 <= 0xFFFFFFFFll;
 }
 
+// a softmax temperature: positive and finite, and so is the 1.0f / temperature the kernels multiply by
+bool softmax_temperature_ok(float t) { return t > 0.f && t <= 3.402823466e+38f && 1.0f / t <= 3.402823466e+38f; }
+
 int fill_step_params(StepParams& p, const TetrisDesc* desc, void* cols, uint64_t* meta, const int32_t* action,
                      int32_t* action_out, const uint8_t* stream, int32_t* cursor, int64_t stream_len, float* obs,
                      int32_t* reward, uint8_t* done, uint8_t* lines, uint8_t* n_valid_next, uint8_t* piece_next,
@@ -342,6 +345,79 @@ int TET_ABI(play_linear)(const TetrisDesc* desc, void* cols, uint64_t* meta, int
   tet::step_keys(seed, step_idx0, p.cfg);
   tet::build_table(desc, &p.tab);
   return backend::launch(desc, p, hip_stream);
+}
+
+// one sampled decision per env from the softmax of its weight row's logits, with log-probability and score
+int TET_ABI(policy_softmax_rows)(const TetrisDesc* desc, const void* cols, const uint64_t* meta, const float* weights,
+                                 int32_t P, const int32_t* rows, float temperature, int32_t* action, float* logp,
+                                 float* score, float* logz, float* logits, uint32_t* status, uint64_t seed,
+                                 uint64_t step_idx, int64_t env_offset, int64_t B, void* hip_stream) {
+  int rc = tet::check_desc(desc);
+  if (rc) return rc;
+  if (!cols || !meta || !weights || !action || !logp) return TETRIS_E_NULL;
+  if (B <= 0 || !batch_fits_u32_offsets(B, B) || P < 1 || (!rows && P < B)) return TETRIS_E_BATCH;
+  if (!softmax_temperature_ok(temperature)) return TETRIS_E_TEMPERATURE;
+  if ((uintptr_t)weights % 16 || (uintptr_t)score % 16) return TETRIS_E_ALIGN;
+  SoftmaxRowsParams p{};
+  p.cols = cols;
+  p.meta = meta;
+  p.weights = weights;
+  p.rows = rows;
+  p.action = action;
+  p.logp = logp;
+  p.score = score;
+  p.logz = logz;
+  p.logits = logits;
+  p.status = status;
+  p.B = B;
+  p.P = P;
+  p.R = desc->num_rows;
+  p.a_max = desc->a_max;
+  p.has_direct_by = desc->has_direct_by;
+  for (int i = 0; i < 8; ++i) p.direct_by[i] = desc->direct_by[i];
+  p.inv_t = 1.0f / temperature;
+  p.key = tet::softmax_key(seed, step_idx);
+  p.env_offset = (uint32_t)env_offset;
+  tet::build_table(desc, &p.tab);
+  return backend::launch(desc, p, hip_stream);
+}
+
+// n_steps sampled steps of every env in one launch: tetris_hip_play_linear with the pick drawn from the softmax
+int TET_ABI(play_softmax)(const TetrisDesc* desc, void* cols, uint64_t* meta, int32_t n_steps, const float* weights,
+                          int32_t P, const int32_t* rows, float temperature, uint32_t* lines_total,
+                          uint32_t* pieces_total, float* logp_total, float* score_total, uint8_t* n_valid,
+                          uint8_t* piece, uint32_t* status, uint64_t seed, uint64_t step_idx0, int64_t env_offset,
+                          int64_t B, void* hip_stream) {
+  int rc = tet::check_desc(desc);
+  if (rc) return rc;
+  if (!cols || !meta || !weights || !lines_total || !pieces_total || !score_total) return TETRIS_E_NULL;
+  if (B <= 0 || !batch_fits_u32_offsets(B, B) || n_steps < 1 || P < 1 || (!rows && P < B)) return TETRIS_E_BATCH;
+  if (!softmax_temperature_ok(temperature)) return TETRIS_E_TEMPERATURE;
+  if ((uintptr_t)weights % 16 || (uintptr_t)score_total % 16) return TETRIS_E_ALIGN;
+  PlaySoftmaxParams q{};
+  PlayParams& p = q.play;
+  p.cols = cols;
+  p.meta = meta;
+  p.weights = weights;
+  p.rows = rows;
+  p.lines_total = lines_total;
+  p.pieces_total = pieces_total;
+  p.n_valid = n_valid;
+  p.piece = piece;
+  p.status = status;
+  p.B = (uint32_t)B;
+  p.env_offset = (uint32_t)env_offset;
+  p.P = P;
+  p.n_steps = n_steps;
+  p.seed = seed;
+  p.step_idx0 = step_idx0;
+  tet::fill_step_cfg(p.cfg, desc, 0, false);  // never resets; no observation is written (direct_by serves the logits)
+  tet::step_keys(seed, step_idx0, p.cfg);
+  tet::build_table(desc, &p.tab);
+  q.logp_total = logp_total;
+  q.score_total = score_total;
+  q.inv_t = 1.0f / temperature;
+  return backend::launch(desc, q, hip_stream);
 }
 
 int TET_ABI(rollouts)(const TetrisDesc* desc, const void* cols, const uint64_t* meta, double* returns, int32_t length,

@@ -6,6 +6,9 @@
 #pragma once
 #include "tetris_core.hpp"
 #include "tetris_table.hpp"
+#if !defined(__HIPCC__)
+#include <math.h>  // expf / logf of the softmax policy's CPU twin (the device has its own)
+#endif
 
 #ifndef TET_LUT10
 #define TET_LUT10 1   // 0: always the 12-row-chunk tables (A/B timing)
@@ -253,6 +256,97 @@ TET_HD void play_step_env(W (&col)[C], uint64_t& meta, const float (&w)[8], cons
   env_step<W, C, NCH, 12, true, SPAD>(col, meta, pick.best_row, false, tab, lut, scratch, sstride, cfg, env, -1, -1, out);
 }
 
+// ---- softmax linear policy: sample, log-probability and score -----------------------------------------
+// (tetris_hip_policy_softmax_rows / tetris_hip_play_softmax; utils.py:26-38 of the reference:
+// compute_action_probabilities and grad_of_log_action_probabilities.)  One pass over afterstates_env, as
+// greedy_pick_env; no row of logits is stored and there is no second pass.  For the non-terminal placement with
+// row index k (the action it is), features f -- multiplied by direct_by when the descriptor has it, i.e. the row
+// tetris_hip_afterstates writes; the greedy calls evaluate undirected features -- and weights w:
+//   logit       u_k = fitness_of(f, w) * inv_t           float32, left to right, inv_t = 1.0f / temperature
+//   online log-sum-exp and expectation over the placements IN THE ORDER THE WALK EMITS THEM:
+//               d = u_k - m;  e = expf(-|d|);  (r, a) = d > 0 ? (e, 1) : (1, e)
+//               s = s * r + a;   g[q] = g[q] * r + a * f[q];   m = max(m, u_k)       (m = -inf, s = 0, g = 0 first)
+//     every product and sum rounded to float32 on its own.  The walk emits the placements that complete a row
+//     AFTER all the others, not in row order, so s and g are float32 sums in that order: the results are
+//     reproducible for a given board, but NOT independent of the order (two boards with the same logits in
+//     another emission order may differ in the last bits).
+//   Gumbel-max draw:   h_k = hash_env(mix32(key ^ ((uint32_t)(k + 1) * 0x9E3779B1u)), env)
+//               U_k = ((h_k >> 8) + 1) * 2^-24   in (0, 1], exact in float32
+//               z_k = u_k - logf(-logf(U_k))               (U_k = 1: z_k = +inf)
+//     with key = hash_key(seed, 4 * step_idx + 1) -- the counter of a step that step_keys leaves free -- and
+//     env the global env index mod 2^32.  The action is the row of maximal z; of exactly equal z the lower row
+//     (GreedyPick's rule).  The picked row's u and f are kept.
+//   results     logz = m + logf(s);  logp = (u_a - m) - logf(s);  score[q] = f_a[q] - g[q] / s
+//     (logp is u_a - logz evaluated in the order that does not cancel: with logits in the thousands u_a - logz in
+//     float32 is good to 1e-3 absolute, (u_a - m) - logf(s) to an ulp of logp)
+//     score is grad_of_log_action_probabilities (utils.py:34-38): the gradient of log p(a) with respect to the
+//     weights WITHOUT the factor 1 / temperature, as upstream.
+// An env without a non-terminal placement: action -1, logp = logz = 0, score = 0.  With one placement s = 1 and
+// g = f exactly, so logp = 0 and score = 0 exactly.  The logits must be finite.
+struct SoftmaxPick {
+  int action;
+  float logp, logz;
+  float score[8];
+};
+TET_HD uint32_t softmax_key(uint64_t seed, uint64_t step_idx) { return hash_key(seed, step_idx * 4u + 1u); }
+// logits_row: NULL or the env's row of a_max floats: entry k = u_k is written for k < n_valid (the caller pads)
+template <typename W, int C, int NCH>
+TET_HD void softmax_pick_env(const W (&col)[C], uint64_t meta, const SetTable& tab, const uint8_t* lut, int R,
+                             const float (&w)[8], float inv_t, bool directed, const float (&direct_by)[8], uint32_t key,
+                             uint32_t env, float* logits_row, SoftmaxPick& out) {
+  float m = -__builtin_inff(), s = 0.f, g[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  float z_best = 0.f, u_a = 0.f, f_a[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  int best_row = -1;
+  afterstates_env<W, C, NCH>(col, meta, tab, lut, R, [&](bool has, int, int, float (&f)[8], int, int row, bool is_valid) {
+    if (!(has && is_valid)) return;
+    if (directed) {
+#pragma unroll
+      for (int q = 0; q < 8; ++q) f[q] = TET_FMUL(f[q], direct_by[q]);
+    }
+    const float u = TET_FMUL(fitness_of(f, w), inv_t);
+    if (logits_row) logits_row[row] = u;
+    const float d = u - m;
+    const float e = expf(-fabsf(d));
+    const bool up = d > 0.f;
+    const float r = up ? e : 1.f, a = up ? 1.f : e;
+    s = TET_FADD(TET_FMUL(s, r), a);
+#pragma unroll
+    for (int q = 0; q < 8; ++q) g[q] = TET_FADD(TET_FMUL(g[q], r), TET_FMUL(a, f[q]));
+    m = up ? u : m;
+    const uint32_t h = hash_env(mix32(key ^ ((uint32_t)(row + 1) * 0x9E3779B1u)), env);
+    const float U = TET_FMUL((float)((h >> 8) + 1u), 5.9604644775390625e-08f);  // 2^-24
+    const float z = u - logf(-logf(U));
+    if (best_row < 0 || z > z_best || (z == z_best && row < best_row)) {
+      z_best = z;
+      best_row = row;
+      u_a = u;
+#pragma unroll
+      for (int q = 0; q < 8; ++q) f_a[q] = f[q];
+    }
+  });
+  out.action = best_row;
+  if (best_row < 0) {
+    out.logp = out.logz = 0.f;
+#pragma unroll
+    for (int q = 0; q < 8; ++q) out.score[q] = 0.f;
+  } else {
+    const float log_s = logf(s);
+    out.logz = TET_FADD(m, log_s);
+    out.logp = (u_a - m) - log_s;  // not u_a - logz: that subtraction cancels at the size of the logits
+#pragma unroll
+    for (int q = 0; q < 8; ++q) out.score[q] = f_a[q] - g[q] / s;
+  }
+}
+// one sampled step of an env that is not over: the draw, then the step (as play_step_env)
+template <typename W, int C, int NCH, bool SPAD>
+TET_HD void play_softmax_step_env(W (&col)[C], uint64_t& meta, const float (&w)[8], float inv_t, uint32_t key_sample,
+                                  const SetTable& tab, const uint8_t* lut, W* scratch, int sstride, const StepCfg& cfg,
+                                  uint32_t env, SoftmaxPick& pick, StepOut& out) {
+  softmax_pick_env<W, C, NCH>(col, meta, tab, lut, cfg.R, w, inv_t, cfg.has_direct_by != 0, cfg.direct_by, key_sample, env,
+                              nullptr, pick);
+  env_step<W, C, NCH, 12, true, SPAD>(col, meta, pick.action, false, tab, lut, scratch, sstride, cfg, env, -1, -1, out);
+}
+
 // ---- the reference's piece sampler on NumPy's legacy global stream ----------------------------------
 // (tetromino.py:12-22 on top of np.random.seed / np.random.permutation): env i is
 // seeded like `np.random.seed(seeds[i])` right before `game.Tetris(...)` is constructed, and row t of
@@ -461,6 +555,36 @@ struct PlayParams {
   tet::SetTable tab;
 };
 
+struct SoftmaxRowsParams {
+  const void* cols;
+  const uint64_t* meta;
+  const float* weights;    // as GreedyRowsParams
+  const int32_t* rows;
+  int32_t* action;
+  float* logp;
+  float* score;            // optional [B][8]
+  float* logz;             // optional [B]
+  float* logits;           // optional [B][a_max]
+  uint32_t* status;        // optional
+  int64_t B;
+  int32_t P;
+  int32_t R;
+  int32_t a_max;
+  int32_t has_direct_by;
+  float direct_by[8];
+  float inv_t;             // 1.0f / temperature
+  uint32_t key;            // tet::softmax_key(seed, step_idx)
+  uint32_t env_offset;     // global env index of env 0 (mod 2^32)
+  tet::SetTable tab;
+};
+
+struct PlaySoftmaxParams {
+  PlayParams play;         // as tetris_hip_play_linear (cfg carries direct_by)
+  float* logp_total;       // optional [B], added to
+  float* score_total;      // [B][8], added to
+  float inv_t;
+};
+
 struct GatherParams {
   const void* src_cols;
   const uint64_t* src_meta;
@@ -479,7 +603,8 @@ struct GatherParams {
 // the blocks travel as kernel arguments (4 KiB at the most), the table inside them
 static_assert(sizeof(StepManyParams) <= 4096 && sizeof(RolloutParams) <= 4096 && sizeof(AfterParams) <= 4096 &&
               sizeof(GreedyParams) <= 4096 && sizeof(ResetParams) <= 4096 && sizeof(GreedyRowsParams) <= 4096 &&
-              sizeof(PlayParams) <= 4096, "kernel argument block over 4 KiB");
+              sizeof(PlayParams) <= 4096 && sizeof(SoftmaxRowsParams) <= 4096 && sizeof(PlaySoftmaxParams) <= 4096,
+              "kernel argument block over 4 KiB");
 
 // bound step call: everything that does not change between steps is prepared once
 struct TetrisStepCall {
@@ -603,6 +728,97 @@ inline void play_linear_host(const PlayParams& p) {
 inline int launch(const TetrisDesc* desc, const PlayParams& p, void*) {
   return host_variant(desc, [&](auto w, auto c, auto nch, auto pack) {
     play_linear_host<decltype(w), decltype(c)::value, decltype(nch)::value, decltype(pack)::value>(p);
+  });
+}
+
+// The CPU twins of softmax_rows_kernel and play_softmax_kernel (tet::softmax_pick_env, tet::play_softmax_step_env);
+// expf / logf are libm's here and the device library's there, so the two agree to rounding, not bit for bit.
+template <typename W, int C, int NCH, bool PACK>
+inline void softmax_rows_host(const SoftmaxRowsParams& p) {
+  const float ninf = -__builtin_inff();
+  for (int64_t i = 0; i < p.B; ++i) {
+    const int32_t row = p.rows ? p.rows[i] : (int32_t)i;
+    if (!tet::weight_row_ok(row, p.P)) {  // untouched, counted
+      if (p.status) p.status[(i >> 6) * 4 + TETRIS_STATUS_INVALID] += 1;
+      continue;
+    }
+    float w[8];
+    tet::load_weight_row(p.weights, row, w);
+    W col[C];
+    tet::load_board<W, C, PACK>(static_cast<const W*>(p.cols), p.B, i, col);
+    float* lrow = p.logits ? p.logits + i * (int64_t)p.a_max : nullptr;
+    tet::SoftmaxPick pick;
+    tet::softmax_pick_env<W, C, NCH>(col, p.meta[i], p.tab, kAfterLut.bytes, p.R, w, p.inv_t, p.has_direct_by != 0,
+                                     p.direct_by, p.key, p.env_offset + (uint32_t)i, lrow, pick);
+    if (lrow)
+      for (int k = tet::popc(tet::meta_mask(p.meta[i]) & p.tab.fullmask[tet::meta_piece(p.meta[i])]); k < p.a_max; ++k) lrow[k] = ninf;
+    p.action[i] = pick.action;
+    p.logp[i] = pick.logp;
+    if (p.logz) p.logz[i] = pick.logz;
+    if (p.score)
+      for (int q = 0; q < 8; ++q) p.score[i * 8 + q] = pick.score[q];
+  }
+}
+inline int launch(const TetrisDesc* desc, const SoftmaxRowsParams& p, void*) {
+  return host_variant(desc, [&](auto w, auto c, auto nch, auto pack) {
+    softmax_rows_host<decltype(w), decltype(c)::value, decltype(nch)::value, decltype(pack)::value>(p);
+  });
+}
+
+template <typename W, int C, int NCH, bool PACK>
+inline void play_softmax_host(const PlaySoftmaxParams& q) {
+  const PlayParams& p = q.play;
+  W* cols = static_cast<W*>(p.cols);
+  const int64_t B = p.B;
+  tet::StepCfg cfg = p.cfg;
+  for (int64_t i = 0; i < B; ++i) {
+    uint32_t* slot = p.status ? p.status + (i >> 6) * 4 : nullptr;
+    const int32_t row = p.rows ? p.rows[i] : (int32_t)i;
+    if (!tet::weight_row_ok(row, p.P)) {  // untouched, counted once per launch
+      if (slot) slot[TETRIS_STATUS_INVALID] += 1;
+      continue;
+    }
+    float w[8];
+    tet::load_weight_row(p.weights, row, w);
+    W col[C], scratch[C];
+    tet::load_board<W, C, PACK>(cols, B, i, col);
+    uint64_t m = p.meta[i];
+    uint32_t lines = 0, pieces = 0;
+    float logp = q.logp_total ? q.logp_total[i] : 0.f, score[8];
+    for (int j = 0; j < 8; ++j) score[j] = q.score_total[i * 8 + j];
+    for (int k = 0; k < p.n_steps; ++k) {
+      if (tet::env_over(m)) continue;  // frozen
+      tet::step_keys(p.seed, p.step_idx0 + (uint64_t)k, cfg);
+      tet::SoftmaxPick pick;
+      tet::StepOut out;
+      tet::play_softmax_step_env<W, C, NCH, false>(col, m, w, q.inv_t, tet::softmax_key(p.seed, p.step_idx0 + (uint64_t)k), p.tab,
+                                                   kAfterLut.bytes, scratch, 1, cfg, p.env_offset + (uint32_t)i, pick, out);
+      if (out.invalid) continue;
+      lines += (uint32_t)out.lines;
+      pieces += 1;
+      logp = TET_FADD(logp, pick.logp);
+      for (int j = 0; j < 8; ++j) score[j] = TET_FADD(score[j], pick.score[j]);
+      if (slot) {
+        slot[TETRIS_STATUS_EPISODES] += out.done;
+        slot[TETRIS_STATUS_LINES] += out.lines;
+        slot[TETRIS_STATUS_STEPS] += 1;
+      }
+    }
+    if (pieces) {
+      tet::store_board<W, C, PACK>(cols, B, i, col);
+      p.meta[i] = m;
+      p.lines_total[i] += lines;
+      p.pieces_total[i] += pieces;
+      if (q.logp_total) q.logp_total[i] = logp;
+      for (int j = 0; j < 8; ++j) q.score_total[i * 8 + j] = score[j];
+    }
+    if (p.n_valid) p.n_valid[i] = (uint8_t)tet::popc(tet::meta_mask(m));
+    if (p.piece) p.piece[i] = (uint8_t)tet::meta_piece(m);
+  }
+}
+inline int launch(const TetrisDesc* desc, const PlaySoftmaxParams& p, void*) {
+  return host_variant(desc, [&](auto w, auto c, auto nch, auto pack) {
+    play_softmax_host<decltype(w), decltype(c)::value, decltype(nch)::value, decltype(pack)::value>(p);
   });
 }
 }  // namespace backend

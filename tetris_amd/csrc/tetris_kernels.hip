@@ -706,6 +706,149 @@ __global__ __launch_bounds__(step_block<W>(), (after_waves<W, C>(TET_STEP_GREEDY
   }
 }
 
+// One sampled decision per env from the softmax of its weight row's logits (tetris_hip_policy_softmax_rows):
+// greedy_rows_kernel with tet::softmax_pick_env as the reduction -- the same launch bounds, the same LDS (tables
+// only, nothing per lane), the same contract for a row outside [0, P).  The feature matrix never reaches memory;
+// an env writes 4 + 4 (+ 32 + 4) bytes, and its row of logits only when asked.
+template <typename W, int C, int NCH>
+__global__ __launch_bounds__(kBlock, (after_waves<W, C>(TET_GREEDY_WAVES))) void softmax_rows_kernel(const SoftmaxRowsParams p) {
+  __shared__ SetTable tab;
+  __shared__ __attribute__((aligned(16))) uint8_t hole_lut[tet::kAfterLutBytes];
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  const bool live = i < p.B;
+  const int32_t row = !live ? -1 : (p.rows ? p.rows[i] : (int32_t)i);
+  const bool ok = live && tet::weight_row_ok(row, p.P);
+  float w[8];
+  tet::load_weight_row(p.weights, ok ? row : 0, w);
+  stage_after_lut(hole_lut);
+  stage_table(tab, p.tab);
+  if (ok) {
+    W col[C];
+    tet::load_board<W, C, (NCH != 0 && !TET_NO_PACK)>(static_cast<const W*>(p.cols), p.B, i, col);
+    const uint64_t meta = p.meta[i];
+    float* lrow = p.logits ? p.logits + i * (int64_t)p.a_max : nullptr;
+    tet::SoftmaxPick pick;
+    tet::softmax_pick_env<W, C, NCH>(col, meta, tab, hole_lut, p.R, w, p.inv_t, p.has_direct_by != 0, p.direct_by, p.key,
+                                     p.env_offset + (uint32_t)i, lrow, pick);
+    if (lrow) {
+      const float ninf = -__builtin_inff();
+      for (int k = tet::popc(tet::meta_mask(meta) & tab.fullmask[tet::meta_piece(meta)]); k < p.a_max; ++k) lrow[k] = ninf;
+    }
+    p.action[i] = pick.action;
+    p.logp[i] = pick.logp;
+    if (p.logz) p.logz[i] = pick.logz;
+    if (p.score) {
+      float4* dst = reinterpret_cast<float4*>(p.score) + 2 * i;
+      dst[0] = make_float4(pick.score[0], pick.score[1], pick.score[2], pick.score[3]);
+      dst[1] = make_float4(pick.score[4], pick.score[5], pick.score[6], pick.score[7]);
+    }
+  }
+  if (p.status) {
+    const unsigned n_bad = wave_count(live && !ok);
+    if ((threadIdx.x & 63) == 0 && n_bad) p.status[(i >> 6) * 4 + TETRIS_STATUS_INVALID] += n_bad;
+  }
+}
+
+// n_steps SAMPLED steps of every env on its weight row in one launch (tetris_hip_play_softmax): play_linear_kernel
+// with the pick replaced by tet::softmax_pick_env.  The running sums of logp and of the score start from the
+// totals in memory and take one float32 addition per placed piece, in step order, so launches compose bit for bit.
+template <typename W, int C, int NCH>
+__global__ __launch_bounds__(step_block<W>(), (after_waves<W, C>(TET_STEP_GREEDY_WAVES))) void play_softmax_kernel(const PlaySoftmaxParams q) {
+  const PlayParams& p = q.play;
+  constexpr int kBlock = step_block<W>();  // shadows the file-wide tile size inside this kernel
+  __shared__ StepLds<W, C, kBlock, 12, true> lds;
+  SetTable& tab = lds.tab;
+  uint8_t* const hole_lut = lds.lut;
+  auto& lane_cols = lds.lane_cols;
+  constexpr bool SPAD = tet::scratch_padded<W, C, NCH, 12, true>();
+  static_assert(sizeof(lds.lane_cols) / sizeof(lds.lane_cols[0]) >= (SPAD ? C + 3 : C), "the unclamped stamp needs its three columns");
+  const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+  const bool live = i < p.B;
+  const uint32_t ii = live ? i : 0;
+  const bool wave_live = (i & ~63u) < p.B;  // (wave-uniform) this wave holds envs: it has a counter slot to keep
+  constexpr bool PACK = NCH != 0 && !TET_NO_PACK;
+  constexpr int NP = tet::n_planes(C, PACK);
+  const uint32_t rec = record_off<W, NP>(ii);
+  W col[C];
+  {
+    W pl[NP];
+#pragma unroll
+    for (int k = 0; k < NP; ++k) pl[k] = ld_off(static_cast<const W*>(p.cols), rec + (uint32_t)(k * 64 * sizeof(W)));
+    tet::unpack_board<W, C, PACK>(pl, col);
+  }
+  uint64_t meta = ld_off(p.meta, ii * 8u);
+  const int32_t row = p.rows ? ld_off(p.rows, ii * 4u) : (int32_t)ii;
+  const bool ok = live && tet::weight_row_ok(row, p.P);
+  float w[8];
+  tet::load_weight_row(p.weights, ok ? row : 0, w);
+  float my_logp = q.logp_total ? ld_off(q.logp_total, ii * 4u) : 0.f;
+  float my_score[8];
+  {
+    const float4 lo = ld_off(reinterpret_cast<const float4*>(q.score_total), ii * 32u);
+    const float4 hi = ld_off(reinterpret_cast<const float4*>(q.score_total), ii * 32u + 16u);
+    my_score[0] = lo.x, my_score[1] = lo.y, my_score[2] = lo.z, my_score[3] = lo.w;
+    my_score[4] = hi.x, my_score[5] = hi.y, my_score[6] = hi.z, my_score[7] = hi.w;
+  }
+  uint4 slot = make_uint4(0, 0, 0, 0);
+  if (p.status && wave_live) slot = ld_off(reinterpret_cast<const uint4*>(p.status), (i >> 6) * 16u);
+  stage_after_lut(hole_lut);
+  stage_table(tab, p.tab);
+  unsigned n_done = 0, n_lines = 0, n_steps = 0;
+  uint32_t my_lines = 0, my_pieces = 0;
+  tet::StepCfg cfg = p.cfg;
+#pragma unroll 1
+  for (int k = 0; k < p.n_steps; ++k) {
+    cfg.key_step = tet::hash_key(p.seed, (p.step_idx0 + (uint64_t)k) * 4u + 0u);  // (== tet::step_keys)
+    cfg.key_policy = tet::hash_key(p.seed, (p.step_idx0 + (uint64_t)k) * 4u + 3u);
+    const uint32_t key_sample = tet::softmax_key(p.seed, p.step_idx0 + (uint64_t)k);
+    bool stepped = false, done = false;
+    int lines = 0;
+    if (ok && !tet::env_over(meta)) {
+      tet::SoftmaxPick pick;
+      tet::StepOut out;
+      tet::play_softmax_step_env<W, C, NCH, SPAD>(col, meta, w, q.inv_t, key_sample, tab, hole_lut, &lane_cols[0][threadIdx.x],
+                                                  kBlock, cfg, p.env_offset + i, pick, out);
+      if (!out.invalid) {
+        stepped = true;
+        done = out.done != 0;
+        lines = out.lines;
+        my_lines += (uint32_t)out.lines;
+        my_pieces += 1;
+        my_logp = TET_FADD(my_logp, pick.logp);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) my_score[j] = TET_FADD(my_score[j], pick.score[j]);
+      }
+    }
+    n_done += wave_count(done);
+    n_lines += wave_sum(3, lines);
+    n_steps += wave_count(stepped);
+  }
+  if (my_pieces) {  // an env that was over at entry keeps every byte
+    W pl[NP];
+    tet::pack_board<W, C, PACK>(col, pl);
+#pragma unroll
+    for (int k = 0; k < NP; ++k) st_off(static_cast<W*>(p.cols), rec + (uint32_t)(k * 64 * sizeof(W)), pl[k]);
+    st_off(p.meta, i * 8u, meta);
+    st_off(p.lines_total, i * 4u, ld_off(p.lines_total, i * 4u) + my_lines);
+    st_off(p.pieces_total, i * 4u, ld_off(p.pieces_total, i * 4u) + my_pieces);
+    if (q.logp_total) st_off(q.logp_total, i * 4u, my_logp);
+    st_off(reinterpret_cast<float4*>(q.score_total), i * 32u, make_float4(my_score[0], my_score[1], my_score[2], my_score[3]));
+    st_off(reinterpret_cast<float4*>(q.score_total), i * 32u + 16u, make_float4(my_score[4], my_score[5], my_score[6], my_score[7]));
+  }
+  if (ok) {
+    if (p.n_valid) st_off(p.n_valid, i, (uint8_t)tet::popc(tet::meta_mask(meta)));
+    if (p.piece) st_off(p.piece, i, (uint8_t)tet::meta_piece(meta));
+  }
+  const unsigned n_inv = wave_count(live && !ok);
+  if (p.status && wave_live && (threadIdx.x & 63) == 0) {
+    slot.x += n_inv;
+    slot.y += n_done;
+    slot.z += n_lines;
+    slot.w += n_steps;
+    st_off(reinterpret_cast<uint4*>(p.status), (i >> 6) * 16u, slot);
+  }
+}
+
 // Tetris.perform_rollouts (game.py:150-160) as a fan-out: one lane per (env, first action) runs its
 // n rollouts back to back with the board in registers; nothing but the mean returns is written.
 // 512 lanes per workgroup: with the 35 KiB of afterstate tables two workgroups = 16 waves fit a CU
@@ -918,6 +1061,22 @@ struct LaunchPlay {
   }
 };
 template <typename W, int C>
+struct LaunchSoftmaxRows {
+  static void run(const SoftmaxRowsParams& p, hipStream_t s) {
+    tet::kernel_variant<W>(p.R, [&](auto nch, auto, auto) {
+      hipLaunchKernelGGL((softmax_rows_kernel<W, C, decltype(nch)::value>), grid_for(p.B), dim3(kBlock), 0, s, p);
+    });
+  }
+};
+template <typename W, int C>
+struct LaunchPlaySoftmax {
+  static void run(const PlaySoftmaxParams& p, hipStream_t s) {
+    tet::kernel_variant<W>(p.play.cfg.R, [&](auto nch, auto, auto) {
+      hipLaunchKernelGGL((play_softmax_kernel<W, C, decltype(nch)::value>), step_grid<W>(p.play.B), dim3(step_block<W>()), 0, s, p);
+    });
+  }
+};
+template <typename W, int C>
 struct LaunchAfter {
   static void run(const AfterParams& p, hipStream_t s) {
     tet::kernel_variant<W>(p.R, [&](auto nch, auto, auto) {
@@ -936,6 +1095,8 @@ template <> struct LaunchId<LaunchGreedy> { static constexpr int value = 5; };
 template <> struct LaunchId<LaunchAfter> { static constexpr int value = 6; };
 template <> struct LaunchId<LaunchGreedyRows> { static constexpr int value = 7; };
 template <> struct LaunchId<LaunchPlay> { static constexpr int value = 8; };
+template <> struct LaunchId<LaunchSoftmaxRows> { static constexpr int value = 9; };
+template <> struct LaunchId<LaunchPlaySoftmax> { static constexpr int value = 10; };
 
 template <template <typename, int> class Launcher, int CC, typename P>
 inline void launch_words(int word_bytes, const void* p, hipStream_t s) {
@@ -955,6 +1116,8 @@ int launch_part(int which, int word_bytes, const void* p, hipStream_t s) {
     case 6: launch_words<LaunchAfter, CC, AfterParams>(word_bytes, p, s); break;
     case 7: launch_words<LaunchGreedyRows, CC, GreedyRowsParams>(word_bytes, p, s); break;
     case 8: launch_words<LaunchPlay, CC, PlayParams>(word_bytes, p, s); break;
+    case 9: launch_words<LaunchSoftmaxRows, CC, SoftmaxRowsParams>(word_bytes, p, s); break;
+    case 10: launch_words<LaunchPlaySoftmax, CC, PlaySoftmaxParams>(word_bytes, p, s); break;
     default: return TETRIS_E_DESC;
   }
   return (int)hipGetLastError();
@@ -1015,6 +1178,8 @@ int launch(const TetrisDesc* d, const GreedyParams& p, void* s) { return dispatc
 int launch(const TetrisDesc* d, const RolloutParams& p, void* s) { return dispatch<LaunchRollouts>(d, p, (hipStream_t)s); }
 int launch(const TetrisDesc* d, const GreedyRowsParams& p, void* s) { return dispatch<LaunchGreedyRows>(d, p, (hipStream_t)s); }
 int launch(const TetrisDesc* d, const PlayParams& p, void* s) { return dispatch<LaunchPlay>(d, p, (hipStream_t)s); }
+int launch(const TetrisDesc* d, const SoftmaxRowsParams& p, void* s) { return dispatch<LaunchSoftmaxRows>(d, p, (hipStream_t)s); }
+int launch(const TetrisDesc* d, const PlaySoftmaxParams& p, void* s) { return dispatch<LaunchPlaySoftmax>(d, p, (hipStream_t)s); }
 
 int launch(const TetrisDesc* d, const GatherParams& p, void* s) {  // one kernel per word size and plane count, whatever the columns
   const bool known = tet::gather_variant(p.n_planes, [&](auto np) {

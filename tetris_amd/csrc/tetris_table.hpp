@@ -160,6 +160,8 @@ inline const char* error_text(int code) {
     case TETRIS_E_STREAM: return "replay stream needs cursor and stream_len > 0";
     case TETRIS_E_STRIDE: return "afterstate strides must be multiples of 4 floats and >= 8";
     case TETRIS_E_OVERLAP: return "source and destination storage overlap (gather into a second cols / meta pair)";
+    case TETRIS_E_ALIGN: return "weights, score and score_total must be 16-byte aligned";
+    case TETRIS_E_TEMPERATURE: return "temperature and 1 / temperature must be positive and finite";
     default: return nullptr;
   }
 }

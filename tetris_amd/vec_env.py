@@ -459,6 +459,92 @@ class VecTetris:
                 break
         return dict(lines=lines.view(torch.uint32), pieces=pieces.view(torch.uint32), done=self.n_valid == 0)
 
+    def _softmax_population(self, weights, rows, temperature, what):
+        """(weights [P, 8], rows or None, temperature) for the softmax calls: a shared vector ``[8]`` becomes P = 1
+        with a cached all-zero row list"""
+        if isinstance(weights, torch.Tensor) and weights.dim() == 1:
+            if weights.shape[0] != 8 or rows is not None:
+                raise ValueError("%s: a shared weight vector has 8 entries and takes no rows" % what)
+            if not hasattr(self, "_zero_rows"):
+                self._zero_rows = torch.zeros(self.batch_size, dtype=torch.int32, device=self.device)
+            weights, rows = weights.reshape(1, 8), self._zero_rows
+        temperature = float(temperature)
+        if not (0.0 < temperature < float("inf")):
+            raise ValueError("%s: temperature must be positive and finite" % what)
+        wt, idx = self._population(weights, rows, what)
+        return wt, idx, temperature
+
+    def sample_actions(self, weights, rows=None, temperature=1.0, score=True, logits=False):
+        """One action per env drawn from the softmax linear policy of the reference's ``utils.py``
+        (``compute_action_probabilities``): p(k) proportional to ``exp(features_k . weights / temperature)`` over
+        the non-terminal placements, with the features ``get_after_states()`` returns (``feature_directions``
+        applied).  ``weights`` is a tensor on the env's device, ``[8]`` (shared) or ``[P, 8]`` with ``rows`` as in
+        :meth:`greedy_actions`.  Returns ``(action int32 [B], logp float32 [B])``, then ``score float32 [B, 8]``
+        when ``score`` -- the gradient of ``logp`` with respect to the weights without the factor
+        ``1 / temperature``, the reference's ``grad_of_log_action_probabilities`` -- then ``logits float32
+        [B, a_max]`` when ``logits`` (``-inf`` past ``n_valid``).  An env that is over gets action -1, logp 0 and
+        score 0.  The feature matrix is never written (``tetris_hip_policy_softmax_rows``).
+
+        The draw is counter-based, keyed on ``seed``, ``step_idx`` and the env index: calling this twice in front
+        of the same step returns the same draw; ``step(action)`` plays it and moves on to the next key.  The
+        returned tensors are buffers the next call overwrites."""
+        wt, idx, temperature = self._softmax_population(weights, rows, temperature, "sample_actions")
+        B, dev = self.batch_size, self.device
+        if not hasattr(self, "_sample_bufs"):
+            self._sample_bufs = dict(action=torch.empty(B, dtype=torch.int32, device=dev),
+                                     logp=torch.empty(B, dtype=torch.float32, device=dev))
+        bufs = self._sample_bufs
+        if score and "score" not in bufs:
+            bufs["score"] = torch.empty((B, 8), dtype=torch.float32, device=dev)
+        if logits and "logits" not in bufs:
+            bufs["logits"] = torch.empty((B, self.a_max), dtype=torch.float32, device=dev)
+        rc = self._lib.policy_softmax_rows(ctypes.byref(self.desc), _ptr(self.cols), _ptr(self.meta), _ptr(wt), wt.shape[0],
+                                           _ptr(idx), temperature, _ptr(bufs["action"]), _ptr(bufs["logp"]),
+                                           _ptr(bufs["score"]) if score else None, None,
+                                           _ptr(bufs["logits"]) if logits else None, _ptr(self.status), self.seed,
+                                           self.step_idx, self.env_offset, B, self._hip_stream())
+        self._lib.check(rc, "tetris_hip_policy_softmax_rows")
+        out = [bufs["action"], bufs["logp"]]
+        if score:
+            out.append(bufs["score"])
+        if logits:
+            out.append(bufs["logits"])
+        return tuple(out)
+
+    def play_sampled(self, weights, rows=None, temperature=1.0, max_steps=1 << 20, chunk=64):
+        """:meth:`play` with every action drawn from the softmax policy of :meth:`sample_actions` instead of the
+        maximum (``tetris_hip_play_softmax``): launches of ``chunk`` steps, one ``n_valid.any()`` read-back per
+        launch, until every game is over or ``max_steps`` steps are played.  Returns ``dict(lines uint32 [B],
+        pieces uint32 [B], logp_total float32 [B], score_total float32 [B, 8], done bool [B])`` for THIS call:
+        ``logp_total`` and ``score_total`` sum ``logp`` and ``score`` over the pieces each env placed -- what
+        episodic REINFORCE needs: ``grad J ~ sum_env (return_env - baseline) * score_total_env``.  Everything
+        :meth:`play` says about resets, finished envs, ``step_idx``, bad rows and replay mode holds here."""
+        if self._stream is not None:
+            raise ValueError("play_sampled draws pieces from the device bag (no replay stream)")
+        max_steps, chunk = int(max_steps), int(chunk)
+        if max_steps < 0 or chunk < 1:
+            raise ValueError("play_sampled: max_steps must be >= 0 and chunk >= 1")
+        wt, idx, temperature = self._softmax_population(weights, rows, temperature, "play_sampled")
+        B, dev = self.batch_size, self.device
+        lines = torch.zeros(B, dtype=torch.int32, device=dev)
+        pieces = torch.zeros(B, dtype=torch.int32, device=dev)
+        logp = torch.zeros(B, dtype=torch.float32, device=dev)
+        score = torch.zeros((B, 8), dtype=torch.float32, device=dev)
+        played = 0
+        while played < max_steps:
+            k = min(chunk, max_steps - played)
+            rc = self._lib.play_softmax(ctypes.byref(self.desc), _ptr(self.cols), _ptr(self.meta), k, _ptr(wt), wt.shape[0],
+                                        _ptr(idx), temperature, _ptr(lines), _ptr(pieces), _ptr(logp), _ptr(score),
+                                        _ptr(self.n_valid), _ptr(self.piece), _ptr(self.status), self.seed, self.step_idx,
+                                        self.env_offset, B, self._hip_stream())
+            self._lib.check(rc, "tetris_hip_play_softmax")
+            self.step_idx += k
+            played += k
+            if not bool(self.n_valid.any()):
+                break
+        return dict(lines=lines.view(torch.uint32), pieces=pieces.view(torch.uint32), logp_total=logp, score_total=score,
+                    done=self.n_valid == 0)
+
     def rollouts(self, length=5, n=5, policy="random", weights=None, pieces=None):
         """Tetris.perform_rollouts (game.py:150-160) for every env and every valid first action:
         ``returns float64 [B, a_max]`` = mean rollout return over ``n`` rollouts of ``length`` steps
