@@ -19,7 +19,19 @@ relative to max(1, |value|); for score relative to max(1, max_k |f_k[q]|)):
 No env of those cases picked anything but the float64 argmax, so 8 x the measurement is 0; TOL_Z is instead 8 x the
 float32 rounding of z itself: z = u - log(-log U) is one float32 subtraction of a float32 u, error <= 2^-24 |z|
 plus the error of the double logarithm (a few 2^-24, absolute), and two placements are compared -- 2^-21 relative
-to max(1, |z|) is 8 x 2^-24."""
+to max(1, |z|) is 8 x 2^-24.
+
+On the directed boards (policy_directed_cases.softmax_rows_directed: the oracle's features, nine-piece catalogue, the
+three temperatures without and with feature_directions) the same bounds hold unchanged -- s and g are float32 sums of
+at most a_max <= 44 same-signed terms, (a_max + 8) x 2^-24 = 3.1e-06 < TOL.  Largest error per kernel variant
+(word, storage, chunks) over its geometries, CPU twin | MI355X, and the envs off the float64 argmax:
+    u32 packed 2 (11)     logz 2.48e-07 | 2.48e-07   logp 6.19e-07 | 6.19e-07   score 8.81e-07 | 8.81e-07   off 0 | 0
+    u32 planes 3 (3)      logz 9.49e-08 | 1.50e-07   logp 5.28e-07 | 5.28e-07   score 8.11e-07 | 8.11e-07   off 0 | 0
+    u64 packed 4 (5)      logz 1.08e-07 | 1.30e-07   logp 5.78e-07 | 6.38e-07   score 8.09e-07 | 8.09e-07   off 0 | 0
+    u64 planes 5 (2)      logz 7.21e-08 | 1.33e-07   logp 4.26e-07 | 4.26e-07   score 6.60e-07 | 6.60e-07   off 0 | 0
+    u64 planes 6 (3)      logz 8.38e-08 | 1.33e-07   logp 5.35e-07 | 5.35e-07   score 9.01e-07 | 9.01e-07   off 0 | 0
+(z64 deficit 0 everywhere.)  The six-step sampled games of play_softmax_directed: logp_total within 9.04e-07 and
+score_total within 1.07e-06 of the float64 sums on both backends, against the bound 6 x TOL."""
 import ctypes
 import os
 
