@@ -232,8 +232,9 @@ __global__ __launch_bounds__(BLK, (step_waves<W, CR>())) void step_kernel(const 
   StepCfg cfg = p.cfg;
   if (p.step_counter) {  // wave-uniform: scalar registers
     const uint64_t c = *p.step_counter;
-    const uint64_t idx = (((uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)(c >> 32)) << 32) |
-                          __builtin_amdgcn_readfirstlane((uint32_t)c)) + p.step_rel;
+    // (the builtin returns int: without the cast a low half of 2^31 or more sign-extends over the high half)
+    const uint64_t idx = (((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(c >> 32)) << 32) |
+                          (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)c)) + p.step_rel;
     cfg.key_step = tet::hash_key(p.seed, idx * 4u + 0u);  // (== tet::step_keys, written out: tetris_entry.hpp)
     cfg.key_policy = tet::hash_key(p.seed, idx * 4u + 3u);
   }
