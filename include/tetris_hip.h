@@ -65,7 +65,7 @@ enum {
   TETRIS_E_BATCH = -6,       /* B <= 0 (tetris_hip_step: or B beyond ~53 M envs per call: 32-bit byte offsets) */
   TETRIS_E_STREAM = -7,      /* replay stream given without cursor / length */
   TETRIS_E_STRIDE = -8,      /* afterstate strides not multiples of 4 floats / too small / matrix beyond 2^32 float4 */
-  TETRIS_E_OVERLAP = -9,     /* tetris_hip_gather_envs: source and destination storage overlap */
+  TETRIS_E_OVERLAP = -9,     /* tetris_hip_gather_envs / tetris_hip_expand_envs: source and destination storage overlap */
   TETRIS_E_ALIGN = -10,      /* softmax calls: weights / score / score_total not 16-byte aligned */
   TETRIS_E_TEMPERATURE = -11 /* softmax calls: temperature (or 1 / temperature) not positive and finite */
 };
@@ -465,6 +465,47 @@ int tetris_hip_refresh(const TetrisDesc* desc, const void* cols, uint64_t* meta,
 int tetris_hip_gather_envs(const TetrisDesc* desc, const void* src_cols, const uint64_t* src_meta, int64_t B_src,
                            void* dst_cols, uint64_t* dst_meta, uint8_t* dst_n_valid, uint8_t* dst_piece,
                            const int32_t* index, uint32_t* status, int64_t B_dst, void* hip_stream);
+
+/*
+ * Expand envs into their afterstates AS ENVS: dst env j := src env parent[j] after placement action[j].  The batch
+ * form of the State objects Tetris.get_after_states builds (game.py:68-69) and Tetris.step adopts (game.py:82-92):
+ * children by (parent, action, next piece) for lookahead over the next piece, beam search, tree expansion, or for
+ * evaluating afterstate boards with something other than the BCTS features.  Both batches share `desc`; src holds
+ * B_src envs and is only read, dst holds B_dst.  For dst env j, with i = parent[j] and a = action[j]:
+ *  i in [0, B_src) and a in [0, n_valid of src env i)
+ *            : dst env j becomes src env i after tetris_hip_step(action = a, auto_reset = 0): the board after landing,
+ *              locking and line clearing; meta with the valid mask of the next piece on that board, the next piece and
+ *              the bag.  A child whose next piece has no non-terminal placement keeps that board, gets mask 0 and
+ *              done = 1 (tetris_hip_play_linear and the other playing calls treat such an env as frozen).
+ *  i == -1   : dst env j is left untouched: no byte of its board or meta and no output element j is written, and
+ *              nothing is counted
+ *  any other i, an a outside that range (every a of a parent that is over), next_piece[j] >= n_pieces
+ *            : dst env j and every output element j are left untouched, and the entry is counted once in
+ *              status[TETRIS_STATUS_INVALID] of dst wave j / 64 (the lazy reporting of tetris_hip_gather_envs).  Only
+ *              this counter is touched: the expansion is no played step, so episodes, lines and steps stay.
+ *  parent / action : int32[B_dst]
+ *  next_piece : uint8[B_dst] list indices, or NULL.
+ *              NULL: the piece is drawn from the PARENT's bag with the key of step `step_idx`, hash_key(seed,
+ *              4 * step_idx), and the parent's env id (env_offset + i) mod 2^32 -- not the child's.  With parent[j] = j
+ *              and B_dst == B_src the call is bit-identical, in every output and in cols and meta, to tetris_hip_step(
+ *              auto_reset = 0) on a copy of src, and all children of one parent get the same piece and bag.
+ *              next_piece[j] = p: the piece is p and the bag is copied unchanged (what a replay stream does); no hash.
+ *  obs       : float[B_dst][8] or NULL: the features of the afterstate as tetris_hip_step writes them (direct_by
+ *              applied); NULL skips their computation
+ *  reward / done / lines / n_valid / piece : as tetris_hip_step writes reward (lines - 1, - 100 when done), done,
+ *              lines, n_valid_next and piece_next; all required
+ *  status    : dst's per-wave counters (uint32[tetris_hip_status_words of B_dst]) or NULL
+ *  env_offset : global index of SRC env 0
+ * The padding lanes of dst's last tile are never written.  If the byte ranges of the two `cols` or of the two `meta`
+ * overlap the call returns TETRIS_E_OVERLAP before anything is launched.  A required pointer that is NULL:
+ * TETRIS_E_NULL.  B_src, B_dst <= 0 or beyond the bound of tetris_hip_step: TETRIS_E_BATCH.  Replay streams are not
+ * part of this call.
+ */
+int tetris_hip_expand_envs(const TetrisDesc* desc, const void* src_cols, const uint64_t* src_meta, int64_t B_src,
+                           void* dst_cols, uint64_t* dst_meta, const int32_t* parent, const int32_t* action,
+                           const uint8_t* next_piece, float* obs, int32_t* reward, uint8_t* done, uint8_t* lines,
+                           uint8_t* n_valid, uint8_t* piece, uint32_t* status, uint64_t seed, uint64_t step_idx,
+                           int64_t env_offset, int64_t B_dst, void* hip_stream);
 
 #ifdef __cplusplus
 }

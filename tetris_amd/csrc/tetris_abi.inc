@@ -3,8 +3,8 @@
 // it for libtetris_hip.so, tests/harness/core_host.cpp for the CPU harness.  The includer defines
 //   TET_ABI(name)       the exported symbol: tetris_hip_##name / tetris_host_##name
 //   namespace backend   what differs between a GPU and a loop over envs, each returning an error code:
-//     launch(const TetrisDesc*, const XParams&, void* stream), overloaded on the ten parameter blocks (the CPU
-//     harness takes GatherParams', GreedyRowsParams' and PlayParams' from tetris_entry.hpp);
+//     launch(const TetrisDesc*, const XParams&, void* stream), overloaded on the parameter blocks (the CPU harness
+//     takes those of the gather, population, softmax and expand calls from tetris_entry.hpp);
 //     pack_done_bits, counter_add, policy_random, numpy_bag_stream, decode, encode, stream_link (the arguments
 //     below); error_text(code) for a positive (runtime) code; kSourceHash.
 // Nothing here launches or touches a buffer: a refused call returns before the backend is reached.
@@ -19,6 +19,17 @@ bool batch_fits_u32_offsets(int64_t B, int64_t max_elems) {
 
 // a softmax temperature: positive and finite, and so is the 1.0f / temperature the kernels multiply by
 bool softmax_temperature_ok(float t) { return t > 0.f && t <= 3.402823466e+38f && 1.0f / t <= 3.402823466e+38f; }
+
+// two batches of one geometry share storage: the byte ranges of their cols or of their meta overlap
+bool batches_overlap(const TetrisDesc* desc, int np, const void* src_cols, const uint64_t* src_meta, int64_t B_src,
+                     const void* dst_cols, const uint64_t* dst_meta, int64_t B_dst) {
+  auto overlap = [](const void* a, int64_t na, const void* b, int64_t nb) {  // byte ranges [a, a + na) and [b, b + nb)
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return x < y + (uintptr_t)nb && y < x + (uintptr_t)na;
+  };
+  return overlap(src_cols, desc->word_bytes * tet::board_words(B_src, np), dst_cols, desc->word_bytes * tet::board_words(B_dst, np)) ||
+         overlap(src_meta, 8 * B_src, dst_meta, 8 * B_dst);
+}
 
 int fill_step_params(StepParams& p, const TetrisDesc* desc, void* cols, uint64_t* meta, const int32_t* action,
                      int32_t* action_out, const uint8_t* stream, int32_t* cursor, int64_t stream_len, float* obs,
@@ -472,13 +483,7 @@ int TET_ABI(gather_envs)(const TetrisDesc* desc, const void* src_cols, const uin
   if (B_src <= 0 || B_dst <= 0 || !batch_fits_u32_offsets(B_src, B_src) || !batch_fits_u32_offsets(B_dst, B_dst))
     return TETRIS_E_BATCH;
   const int np = tet::n_planes(desc->num_columns, tet::board_packed(desc->word_bytes, desc->num_rows));
-  auto overlap = [](const void* a, int64_t na, const void* b, int64_t nb) {  // byte ranges [a, a + na) and [b, b + nb)
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return x < y + (uintptr_t)nb && y < x + (uintptr_t)na;
-  };
-  if (overlap(src_cols, desc->word_bytes * tet::board_words(B_src, np), dst_cols, desc->word_bytes * tet::board_words(B_dst, np)) ||
-      overlap(src_meta, 8 * B_src, dst_meta, 8 * B_dst))
-    return TETRIS_E_OVERLAP;
+  if (batches_overlap(desc, np, src_cols, src_meta, B_src, dst_cols, dst_meta, B_dst)) return TETRIS_E_OVERLAP;
   GatherParams p{};
   p.src_cols = src_cols;
   p.src_meta = src_meta;
@@ -494,6 +499,44 @@ int TET_ABI(gather_envs)(const TetrisDesc* desc, const void* src_cols, const uin
   tet::SetTable tab;
   tet::build_table(desc, &tab);
   for (int i = 0; i < desc->n_pieces; ++i) p.fullmask[i] = tab.fullmask[i];
+  return backend::launch(desc, p, hip_stream);
+}
+
+// dst env j := src env parent[j] after placement action[j], the next piece dictated or drawn from the parent's bag
+int TET_ABI(expand_envs)(const TetrisDesc* desc, const void* src_cols, const uint64_t* src_meta, int64_t B_src,
+                         void* dst_cols, uint64_t* dst_meta, const int32_t* parent, const int32_t* action,
+                         const uint8_t* next_piece, float* obs, int32_t* reward, uint8_t* done, uint8_t* lines,
+                         uint8_t* n_valid, uint8_t* piece, uint32_t* status, uint64_t seed, uint64_t step_idx,
+                         int64_t env_offset, int64_t B_dst, void* hip_stream) {
+  int rc = tet::check_desc(desc);
+  if (rc) return rc;
+  if (!src_cols || !src_meta || !dst_cols || !dst_meta || !parent || !action || !reward || !done || !lines || !n_valid || !piece)
+    return TETRIS_E_NULL;
+  if (B_src <= 0 || B_dst <= 0 || !batch_fits_u32_offsets(B_src, B_src) || !batch_fits_u32_offsets(B_dst, B_dst))
+    return TETRIS_E_BATCH;
+  const int np = tet::n_planes(desc->num_columns, tet::board_packed(desc->word_bytes, desc->num_rows));
+  if (batches_overlap(desc, np, src_cols, src_meta, B_src, dst_cols, dst_meta, B_dst)) return TETRIS_E_OVERLAP;
+  ExpandParams p{};
+  p.src_cols = src_cols;
+  p.src_meta = src_meta;
+  p.dst_cols = dst_cols;
+  p.dst_meta = dst_meta;
+  p.parent = parent;
+  p.action = action;
+  p.next_piece = next_piece;
+  p.obs = obs;
+  p.reward = reward;
+  p.done = done;
+  p.lines = lines;
+  p.n_valid = n_valid;
+  p.piece = piece;
+  p.status = status;
+  p.B_src = (uint32_t)B_src;
+  p.B_dst = (uint32_t)B_dst;
+  p.env_offset = (uint32_t)env_offset;
+  tet::fill_step_cfg(p.cfg, desc, 0, obs != nullptr);  // never resets: a child that is over keeps its board
+  tet::step_keys(seed, step_idx, p.cfg);
+  tet::build_table(desc, &p.tab);
   return backend::launch(desc, p, hip_stream);
 }
 

@@ -194,6 +194,26 @@ inline bool gather_variant(int np, F&& f) {
   }
 }
 
+// ---- expansion of envs into their afterstates --------------------------------------------------------
+// dst env j := src env parent[j] after placement action[j] (tetris_hip_expand_envs): what a step without auto-reset
+// makes of the parent, written to ANOTHER batch, with the next piece either dictated (next_piece, env_step's replay
+// `draw`: the bag is kept) or drawn from the parent's bag under the parent's env id.  An entry is kept (parent == -1:
+// nothing written, nothing counted), run, or bad (any other parent outside [0, B_src), a piece outside the set: nothing
+// written, counted); a run entry whose action is no placement of the parent -- every action of a parent that is over --
+// comes back from the body with out.invalid set and is bad too.
+enum { kExpandKeep = 0, kExpandRun = 1, kExpandBad = 2 };
+TET_HD int expand_entry(int32_t parent, uint32_t B_src, int next_piece, int n_pieces) {
+  if (parent == -1) return kExpandKeep;
+  return (parent < 0 || (uint32_t)parent >= B_src || next_piece >= n_pieces) ? kExpandBad : kExpandRun;
+}
+// the per-env body on the parent's unpacked board and meta: col / meta become the child's unless out.invalid.
+// next_piece < 0: drawn.  `env` is the PARENT's global id, so every child of one parent draws the same piece.
+template <typename W, int C, int NCH, int CR, bool SPAD>
+TET_HD void expand_env(W (&col)[C], uint64_t& meta, int action, int next_piece, const SetTable& tab, const uint8_t* lut,
+                       W* scratch, int sstride, const StepCfg& cfg, uint32_t env, StepOut& out) {
+  env_step<W, C, NCH, CR, false, SPAD>(col, meta, action, false, tab, lut, scratch, sstride, cfg, env, next_piece, -1, out);
+}
+
 // ---- rollout fan-out ------------------------------------------------------------------------------
 // Mean return of the n rollouts of (env i, first action a0); NaN where a0 is not an action of the env.
 // Rollout r has the global id uid (its low word keys the hashes, its high word the key) and reads its
@@ -600,10 +620,33 @@ struct GatherParams {
   uint64_t fullmask[tet::kMetaPieces];  // of the set's table (tet::SetTable); zero past the last piece
 };
 
+struct ExpandParams {
+  const void* src_cols;
+  const uint64_t* src_meta;
+  void* dst_cols;
+  uint64_t* dst_meta;
+  const int32_t* parent;     // [B_dst]: src env, -1 = keep
+  const int32_t* action;     // [B_dst]: placement of that env
+  const uint8_t* next_piece; // [B_dst] list indices, or NULL: drawn from the parent's bag
+  float* obs;                // optional [B_dst][8]
+  int32_t* reward;
+  uint8_t* done;
+  uint8_t* lines;
+  uint8_t* n_valid;
+  uint8_t* piece;
+  uint32_t* status;          // dst's per-wave counters or NULL
+  uint32_t B_src;
+  uint32_t B_dst;
+  uint32_t env_offset;       // global env index of SRC env 0 (mod 2^32)
+  tet::StepCfg cfg;          // auto_reset = 0; key_step is the step's
+  tet::SetTable tab;
+};
+
 // the blocks travel as kernel arguments (4 KiB at the most), the table inside them
 static_assert(sizeof(StepManyParams) <= 4096 && sizeof(RolloutParams) <= 4096 && sizeof(AfterParams) <= 4096 &&
               sizeof(GreedyParams) <= 4096 && sizeof(ResetParams) <= 4096 && sizeof(GreedyRowsParams) <= 4096 &&
-              sizeof(PlayParams) <= 4096 && sizeof(SoftmaxRowsParams) <= 4096 && sizeof(PlaySoftmaxParams) <= 4096,
+              sizeof(PlayParams) <= 4096 && sizeof(SoftmaxRowsParams) <= 4096 && sizeof(PlaySoftmaxParams) <= 4096 &&
+              sizeof(ExpandParams) <= 4096,
               "kernel argument block over 4 KiB");
 
 // bound step call: everything that does not change between steps is prepared once
@@ -642,16 +685,16 @@ inline int launch(const TetrisDesc* desc, const GatherParams& p, void*) {
 
 // The CPU twins of greedy_rows_kernel and play_linear_kernel: loops over envs on the shared bodies
 // (tet::greedy_pick_env, tet::play_step_env), on the instantiation the library launches for the geometry.
-// f(W{}, IntConst<C>, IntConst<NCH>, BoolConst<PACK>)
+// f(W{}, IntConst<C>, IntConst<NCH>, IntConst<CR>, BoolConst<PACK>)
 template <typename F>
 inline int host_variant(const TetrisDesc* desc, F&& f) {
   switch (desc->num_columns) {
 #define TET_X(CC)                                                                                                  \
   case CC:                                                                                                         \
     if (desc->word_bytes == 4)                                                                                     \
-      tet::kernel_variant<uint32_t>(desc->num_rows, [&](auto nch, auto, auto pack) { f(uint32_t{}, tet::IntConst<CC>{}, nch, pack); }); \
+      tet::kernel_variant<uint32_t>(desc->num_rows, [&](auto nch, auto cr, auto pack) { f(uint32_t{}, tet::IntConst<CC>{}, nch, cr, pack); }); \
     else                                                                                                           \
-      tet::kernel_variant<uint64_t>(desc->num_rows, [&](auto nch, auto, auto pack) { f(uint64_t{}, tet::IntConst<CC>{}, nch, pack); }); \
+      tet::kernel_variant<uint64_t>(desc->num_rows, [&](auto nch, auto cr, auto pack) { f(uint64_t{}, tet::IntConst<CC>{}, nch, cr, pack); }); \
     return TETRIS_OK;
     TET_COLUMNS(TET_X)
 #undef TET_X
@@ -678,7 +721,7 @@ inline void greedy_rows_host(const GreedyRowsParams& p) {
   }
 }
 inline int launch(const TetrisDesc* desc, const GreedyRowsParams& p, void*) {
-  return host_variant(desc, [&](auto w, auto c, auto nch, auto pack) {
+  return host_variant(desc, [&](auto w, auto c, auto nch, auto, auto pack) {
     greedy_rows_host<decltype(w), decltype(c)::value, decltype(nch)::value, decltype(pack)::value>(p);
   });
 }
@@ -726,7 +769,7 @@ inline void play_linear_host(const PlayParams& p) {
   }
 }
 inline int launch(const TetrisDesc* desc, const PlayParams& p, void*) {
-  return host_variant(desc, [&](auto w, auto c, auto nch, auto pack) {
+  return host_variant(desc, [&](auto w, auto c, auto nch, auto, auto pack) {
     play_linear_host<decltype(w), decltype(c)::value, decltype(nch)::value, decltype(pack)::value>(p);
   });
 }
@@ -760,7 +803,7 @@ inline void softmax_rows_host(const SoftmaxRowsParams& p) {
   }
 }
 inline int launch(const TetrisDesc* desc, const SoftmaxRowsParams& p, void*) {
-  return host_variant(desc, [&](auto w, auto c, auto nch, auto pack) {
+  return host_variant(desc, [&](auto w, auto c, auto nch, auto, auto pack) {
     softmax_rows_host<decltype(w), decltype(c)::value, decltype(nch)::value, decltype(pack)::value>(p);
   });
 }
@@ -817,8 +860,49 @@ inline void play_softmax_host(const PlaySoftmaxParams& q) {
   }
 }
 inline int launch(const TetrisDesc* desc, const PlaySoftmaxParams& p, void*) {
-  return host_variant(desc, [&](auto w, auto c, auto nch, auto pack) {
+  return host_variant(desc, [&](auto w, auto c, auto nch, auto, auto pack) {
     play_softmax_host<decltype(w), decltype(c)::value, decltype(nch)::value, decltype(pack)::value>(p);
+  });
+}
+
+// The CPU twin of expand_kernel: a loop over dst envs on tet::expand_entry / tet::expand_env, on the instantiation and
+// the feature tables step_kernel runs for the geometry.
+template <typename W, int C, int NCH, int CR, bool PACK>
+inline void expand_host(const ExpandParams& p) {
+  const uint8_t* lut = CR == 10 ? kFeatureLut10.bytes : kFeatureLut.bytes;
+  for (int64_t j = 0; j < (int64_t)p.B_dst; ++j) {
+    const int32_t parent = p.parent[j];
+    const int np = p.next_piece ? (int)p.next_piece[j] : -1;
+    const int entry = tet::expand_entry(parent, p.B_src, np, p.cfg.n_pieces);
+    if (entry == tet::kExpandKeep) continue;
+    bool bad = entry == tet::kExpandBad;
+    W col[C], scratch[C];
+    uint64_t m = 0;
+    tet::StepOut out;
+    if (!bad) {
+      tet::load_board<W, C, PACK>(static_cast<const W*>(p.src_cols), p.B_src, parent, col);
+      m = p.src_meta[parent];
+      tet::expand_env<W, C, NCH, CR, false>(col, m, p.action[j], np, p.tab, lut, scratch, 1, p.cfg, p.env_offset + (uint32_t)parent, out);
+      bad = out.invalid != 0;
+    }
+    if (bad) {  // untouched, counted
+      if (p.status) p.status[(j >> 6) * 4 + TETRIS_STATUS_INVALID] += 1;
+      continue;
+    }
+    tet::store_board<W, C, PACK>(static_cast<W*>(p.dst_cols), p.B_dst, j, col);
+    p.dst_meta[j] = m;
+    if (p.obs)
+      for (int k = 0; k < 8; ++k) p.obs[j * 8 + k] = out.obs[k];
+    p.reward[j] = out.reward;
+    p.done[j] = (uint8_t)out.done;
+    p.lines[j] = (uint8_t)out.lines;
+    p.n_valid[j] = (uint8_t)out.n_valid;
+    p.piece[j] = (uint8_t)out.piece;
+  }
+}
+inline int launch(const TetrisDesc* desc, const ExpandParams& p, void*) {
+  return host_variant(desc, [&](auto w, auto c, auto nch, auto cr, auto pack) {
+    expand_host<decltype(w), decltype(c)::value, decltype(nch)::value, decltype(cr)::value, decltype(pack)::value>(p);
   });
 }
 }  // namespace backend

@@ -909,6 +909,71 @@ __global__ __launch_bounds__(kBlock) void gather_envs_kernel(const GatherParams 
   }
 }
 
+// dst env j := src env parent[j] after placement action[j] (tetris_hip_expand_envs): gather_envs_kernel's scattered
+// read joined to step_kernel's body, on step_kernel's instantiation, feature tables and 256-env tile, so the board of
+// a child goes from the parent's registers to dst without a copy in HBM in between.  One lane per dst env.  The lane's
+// three index loads are coalesced; the gathered plane loads (a compile-time count) and the gathered meta load follow
+// back to back, clamped to src env 0 for the lanes that run nothing, so that the staging and its barrier sit outside
+// every branch.  Kept and bad entries and the lanes past B_dst store nothing; bad entries go to the wave's counter slot
+// like gather_envs_kernel's.
+template <typename W, int C, int NCH, int CR, bool PACK>
+__global__ __launch_bounds__(kBlock, (step_waves<W, CR>())) void expand_kernel(const ExpandParams p) {
+  __shared__ StepLds<W, C, kBlock, CR> lds;
+  SetTable& tab = lds.tab;
+  uint8_t* const hole_lut = lds.lut;
+  auto& lane_cols = lds.lane_cols;
+  constexpr bool SPAD = tet::scratch_padded<W, C, NCH, CR>();
+  static_assert(sizeof(lds.lane_cols) / sizeof(lds.lane_cols[0]) >= (SPAD ? C + 3 : C), "the unclamped stamp needs its three columns");
+  static_assert(PACK == (NCH != 0 && !TET_NO_PACK), "a counted-chunk variant runs exactly on packed boards");
+  constexpr int NP = tet::n_planes(C, PACK);
+  const uint32_t j = blockIdx.x * kBlock + threadIdx.x;
+  const bool live = j < p.B_dst;
+  const uint32_t jj = live ? j : 0;
+  const int32_t parent = live ? ld_off(p.parent, jj * 4u) : -1;
+  const int action = ld_off(p.action, jj * 4u);
+  const int next_piece = p.next_piece ? (int)ld_off(p.next_piece, jj) : -1;
+  const int entry = tet::expand_entry(parent, p.B_src, next_piece, p.cfg.n_pieces);
+  const bool run = entry == tet::kExpandRun;
+  const uint32_t ii = run ? (uint32_t)parent : 0u;  // (a src env every launch has)
+  const uint32_t src_rec = record_off<W, NP>(ii);
+  W pl[NP];
+#pragma unroll
+  for (int q = 0; q < NP; ++q) pl[q] = ld_off(static_cast<const W*>(p.src_cols), src_rec + (uint32_t)(q * 64 * sizeof(W)));
+  uint64_t meta = ld_off(p.src_meta, ii * 8u);
+  stage_hole_lut<W, C, NCH, CR>(hole_lut);
+  stage_table(tab, p.tab);
+  bool bad = entry == tet::kExpandBad;
+  if (run) {
+    W col[C];
+    tet::unpack_board<W, C, PACK>(pl, col);
+    tet::StepOut out;
+    tet::expand_env<W, C, NCH, CR, SPAD>(col, meta, action, next_piece, tab, hole_lut, &lane_cols[0][threadIdx.x], kBlock, p.cfg,
+                                         p.env_offset + ii, out);
+    bad = out.invalid != 0;
+    if (!bad) {
+      tet::pack_board<W, C, PACK>(col, pl);
+      const uint32_t dst_rec = record_off<W, NP>(j);
+#pragma unroll
+      for (int q = 0; q < NP; ++q) st_off(static_cast<W*>(p.dst_cols), dst_rec + (uint32_t)(q * 64 * sizeof(W)), pl[q]);
+      st_off(p.dst_meta, j * 8u, meta);
+      if (p.obs) {
+        float4* o4 = reinterpret_cast<float4*>(p.obs);
+        st_off(o4, j * 32u, make_float4(out.obs[0], out.obs[1], out.obs[2], out.obs[3]));
+        st_off(o4, j * 32u + 16u, make_float4(out.obs[4], out.obs[5], out.obs[6], out.obs[7]));
+      }
+      st_off(p.reward, j * 4u, (int32_t)out.reward);
+      st_off(p.done, j, (uint8_t)out.done);
+      st_off(p.lines, j, (uint8_t)out.lines);
+      st_off(p.n_valid, j, (uint8_t)out.n_valid);
+      st_off(p.piece, j, (uint8_t)out.piece);
+    }
+  }
+  if (p.status) {
+    const unsigned n_bad = wave_count(bad);
+    if ((threadIdx.x & 63) == 0 && n_bad) p.status[(j >> 6) * 4 + TETRIS_STATUS_INVALID] += n_bad;
+  }
+}
+
 __global__ void counter_add_kernel(uint64_t* counter, uint64_t n) { *counter += n; }
 
 // done flags -> bitmask (bit i % 8 of byte i / 8): one ballot per wavefront, eight bytes per store.
@@ -1085,6 +1150,15 @@ struct LaunchAfter {
     });
   }
 };
+template <typename W, int C>
+struct LaunchExpand {
+  static void run(const ExpandParams& p, hipStream_t s) {
+    tet::kernel_variant<W>(p.cfg.R, [&](auto nch, auto cr, auto pack) {
+      hipLaunchKernelGGL((expand_kernel<W, C, decltype(nch)::value, decltype(cr)::value, decltype(pack)::value>), grid_for(p.B_dst),
+                         dim3(kBlock), 0, s, p);
+    });
+  }
+};
 
 
 template <> struct LaunchId<LaunchStep> { static constexpr int value = 0; };
@@ -1098,6 +1172,7 @@ template <> struct LaunchId<LaunchGreedyRows> { static constexpr int value = 7; 
 template <> struct LaunchId<LaunchPlay> { static constexpr int value = 8; };
 template <> struct LaunchId<LaunchSoftmaxRows> { static constexpr int value = 9; };
 template <> struct LaunchId<LaunchPlaySoftmax> { static constexpr int value = 10; };
+template <> struct LaunchId<LaunchExpand> { static constexpr int value = 11; };
 
 template <template <typename, int> class Launcher, int CC, typename P>
 inline void launch_words(int word_bytes, const void* p, hipStream_t s) {
@@ -1119,6 +1194,7 @@ int launch_part(int which, int word_bytes, const void* p, hipStream_t s) {
     case 8: launch_words<LaunchPlay, CC, PlayParams>(word_bytes, p, s); break;
     case 9: launch_words<LaunchSoftmaxRows, CC, SoftmaxRowsParams>(word_bytes, p, s); break;
     case 10: launch_words<LaunchPlaySoftmax, CC, PlaySoftmaxParams>(word_bytes, p, s); break;
+    case 11: launch_words<LaunchExpand, CC, ExpandParams>(word_bytes, p, s); break;
     default: return TETRIS_E_DESC;
   }
   return (int)hipGetLastError();
@@ -1181,6 +1257,7 @@ int launch(const TetrisDesc* d, const GreedyRowsParams& p, void* s) { return dis
 int launch(const TetrisDesc* d, const PlayParams& p, void* s) { return dispatch<LaunchPlay>(d, p, (hipStream_t)s); }
 int launch(const TetrisDesc* d, const SoftmaxRowsParams& p, void* s) { return dispatch<LaunchSoftmaxRows>(d, p, (hipStream_t)s); }
 int launch(const TetrisDesc* d, const PlaySoftmaxParams& p, void* s) { return dispatch<LaunchPlaySoftmax>(d, p, (hipStream_t)s); }
+int launch(const TetrisDesc* d, const ExpandParams& p, void* s) { return dispatch<LaunchExpand>(d, p, (hipStream_t)s); }
 
 int launch(const TetrisDesc* d, const GatherParams& p, void* s) {  // one kernel per word size and plane count, whatever the columns
   const bool known = tet::gather_variant(p.n_planes, [&](auto np) {

@@ -696,23 +696,149 @@ class VecTetris:
             env.copy_envs_from(bank, torch.where(env.done, draws, -1))
 
         To permute or select within ONE batch use :meth:`gather_`; for a new batch :meth:`fork`."""
-        if not isinstance(src, VecTetris):
-            raise ValueError("copy_envs_from: src must be a VecTetris")
-        if src is self:
-            raise ValueError("copy_envs_from: src is this env; the copy cannot run in place -- use gather_(index)")
-        if (src.num_columns, src.num_rows, list(src.piece_names)) != (self.num_columns, self.num_rows,
-                                                                       list(self.piece_names)):
-            raise ValueError("copy_envs_from: src is %dx%d %s, this env %dx%d %s" % (
-                src.num_columns, src.num_rows, list(src.piece_names), self.num_columns, self.num_rows,
-                list(self.piece_names)))
-        if src.device != self.device:
-            raise ValueError("copy_envs_from: src lives on %s, this env on %s" % (src.device, self.device))
-        if src._stream is not None or self._stream is not None:
-            raise ValueError("copy_envs_from: an env in replay mode (piece_stream / numpy_seeds) cannot take part: "
-                             "its stream columns do not travel")
+        self._check_source(src, "copy_envs_from", "the copy cannot run in place -- use gather_(index)")
         idx = self._gather_index(index, "copy_envs_from")
         self._gather_call(src.cols, src.meta, src.batch_size, self.cols, self.meta, idx, self.status)
         return self
+
+    def _check_source(self, src, what, in_place):
+        """what a call that reads envs of ``src`` into this batch asks of the pair"""
+        if not isinstance(src, VecTetris):
+            raise ValueError("%s: src must be a VecTetris" % what)
+        if src is self:
+            raise ValueError("%s: src is this env; %s" % (what, in_place))
+        if (src.num_columns, src.num_rows, list(src.piece_names)) != (self.num_columns, self.num_rows,
+                                                                       list(self.piece_names)):
+            raise ValueError("%s: src is %dx%d %s, this env %dx%d %s" % (
+                what, src.num_columns, src.num_rows, list(src.piece_names), self.num_columns, self.num_rows,
+                list(self.piece_names)))
+        if src.device != self.device:
+            raise ValueError("%s: src lives on %s, this env on %s" % (what, src.device, self.device))
+        if src._stream is not None or self._stream is not None:
+            raise ValueError("%s: an env in replay mode (piece_stream / numpy_seeds) cannot take part: "
+                             "its stream columns do not travel" % what)
+
+    # -- afterstates as envs: children by (parent, action, next piece) ---------------------------------
+    def expand_from(self, src, parent, action, next_piece=None, step_idx=None):
+        """``self[j] := src[parent[j]]`` after placement ``action[j]``, in place (``tetris_hip_expand_envs``): the
+        afterstate POSITIONS of ``src`` as envs of this batch -- the ``State`` objects the reference's
+        ``get_after_states`` builds and ``step`` adopts (game.py:68-69, 82-92) -- for lookahead over the next
+        piece, beam search, tree expansion, or a value network on :meth:`boards`.  One kernel; the board of a
+        child never exists as a copy of its parent.  ``src`` is only read.
+
+        ``parent`` and ``action`` are ``[batch_size]`` ints.  Env j becomes what ``src[parent[j]]`` is after
+        ``step(action[j])`` without auto-reset, and ``obs / reward / done / lines / n_valid / piece`` of this
+        batch are filled as a step fills them.  ``next_piece`` is ``uint8 [batch_size]`` list indices (or one
+        int for all): the piece each child faces, its bag copied from the parent unchanged.  ``None`` draws the
+        piece from the PARENT's bag exactly as ``src.step()`` would at ``step_idx`` (default ``src.step_idx``)
+        -- with ``src``'s seed and the parent's global env index, so every child of one parent gets the same
+        piece, and ``parent = arange(B)`` reproduces ``src.step(action)`` bit for bit in another batch.
+
+        ``parent[j] == -1`` leaves env j and its outputs as they are.  Any other parent outside
+        ``[0, src.batch_size)``, an action that is no placement of the parent (every action of a parent that is
+        over) or a piece outside the set leaves env j too and is counted, so that :meth:`check` raises
+        IndexError.  A child without a non-terminal placement of its piece has ``done`` set and ``n_valid`` 0;
+        :meth:`play` and :meth:`greedy_actions` treat it as over.  ``src`` must be another VecTetris on this
+        device with the same columns, rows and piece set; replay mode is refused.  This batch's ``step_idx`` is
+        left alone.  Returns ``self``."""
+        self._check_source(src, "expand_from", "a child batch is another VecTetris -- see expand()")
+        par = self._gather_index(parent, "expand_from")
+        act = self._gather_index(action, "expand_from")
+        nxt = None
+        if next_piece is not None:
+            if isinstance(next_piece, int):
+                next_piece = torch.full((self.batch_size,), next_piece if 0 <= next_piece < 255 else 255,
+                                        dtype=torch.uint8, device=self.device)
+            nxt = torch.as_tensor(next_piece, device=self.device)
+            if nxt.shape != (self.batch_size,) or nxt.dtype.is_floating_point or nxt.dtype.is_complex or nxt.dtype == torch.bool:
+                raise ValueError("expand_from: next_piece must be [batch_size] = [%d] list indices" % self.batch_size)
+            if nxt.dtype != torch.uint8:  # an index no uint8 holds is outside every piece set
+                nxt = torch.where((nxt < 0) | (nxt > 255), torch.full_like(nxt, 255), nxt).to(torch.uint8)
+            nxt = nxt.contiguous()
+        if not self._views_own:
+            self._own_views()
+        rc = self._lib.expand_envs(ctypes.byref(self.desc), _ptr(src.cols), _ptr(src.meta), src.batch_size,
+                                   _ptr(self.cols), _ptr(self.meta), _ptr(par), _ptr(act), _ptr(nxt),
+                                   _ptr(self._obs_buf) if self.compute_obs else None, _ptr(self._reward_buf),
+                                   _ptr(self._done_buf), _ptr(self._lines_buf), _ptr(self.n_valid), _ptr(self.piece),
+                                   _ptr(self.status), src.seed, src.step_idx if step_idx is None else int(step_idx),
+                                   src.env_offset, self.batch_size, self._hip_stream())
+        self._lib.check(rc, "tetris_hip_expand_envs")
+        return self
+
+    def _dense_children(self):
+        """(parent int32 [B * a_max], action int32 [B * a_max], present bool [B, a_max]) of the dense expansion:
+        child i * a_max + k is placement k of env i, absent (parent -1) where k >= n_valid[i]"""
+        B, A, dev = self.batch_size, self.a_max, self.device
+        k = torch.arange(A, dtype=torch.int32, device=dev)
+        present = k[None, :] < self.n_valid[:, None].to(torch.int32)
+        own = torch.arange(B, dtype=torch.int32, device=dev)[:, None].expand(B, A)
+        parent = torch.where(present, own, torch.full_like(own, -1)).reshape(-1).contiguous()
+        return parent, k.repeat(B), present
+
+    def _child_batch(self, **kw):
+        cfg = dict(auto_reset=self.auto_reset, compute_obs=self.compute_obs)
+        cfg.update(kw)
+        return VecTetris(self.num_columns, self.num_rows, self.batch_size * self.a_max, device=self.device,
+                         pieces=list(self.piece_names), seed=self.seed, feature_directions=self.feature_directions,
+                         env_offset=self.env_offset, afterstate_layout=self.afterstate_layout, **cfg)
+
+    def expand(self, next_piece=None):
+        """Every placement of every env as an env: returns ``(child, present)`` -- a NEW VecTetris of
+        ``batch_size * a_max`` envs with the configuration :meth:`fork` passes on, child ``i * a_max + k`` being
+        env i after placement k (:meth:`expand_from`), and ``present`` ``bool [B, a_max]``: ``k < n_valid[i]``.
+        Absent children are freshly reset envs and are not counted as errors.  ``next_piece`` is one list index
+        every child gets, or ``None``: each child faces the piece its parent would draw at this step, and
+        ``child.step_idx = step_idx + 1`` (else ``step_idx``), so the children play on as the parent would have.
+        This env is unchanged.
+
+        Row k of ``get_after_states()`` is ``child.obs[i * a_max + k]``; ``child.boards()`` are the afterstate
+        boards, ``child.reward / done / lines`` what the placement earns."""
+        if self._stream is not None:
+            raise ValueError("expand: an env in replay mode (piece_stream / numpy_seeds) cannot be expanded: its "
+                             "stream columns do not travel")
+        if next_piece is not None:
+            next_piece = int(next_piece)
+            if not 0 <= next_piece < len(self.piece_names):
+                raise ValueError("expand: next_piece must be a list index below %d" % len(self.piece_names))
+        parent, action, present = self._dense_children()
+        child = self._child_batch()
+        child.expand_from(self, parent, action, next_piece)
+        child.step_idx = self.step_idx + (1 if next_piece is None else 0)
+        return child, present
+
+    def two_ply_values(self, weights=None):
+        """``float32 [B, a_max, n_pieces]``: ``value[i, k, p]`` is the best linear fitness (``weights``: 8 floats,
+        default the BCTS vector of game.py:111-118; :meth:`greedy_actions`' ``best_value``) among the
+        non-terminal placements of piece ``p`` on the board env i has after ITS placement k -- the second ply of
+        a two-piece lookahead.  ``-inf`` where that child is over with piece ``p``, ``NaN`` where
+        ``k >= n_valid[i]``.  One :meth:`expand_from` into one child batch (kept for the next call) and one
+        :meth:`greedy_actions` per piece; this env is unchanged.
+
+        The two-piece-lookahead action averages over the pieces that can come next and takes the best first
+        placement.  With a uniform bag::
+
+            v = env.two_ply_values()
+            action = torch.nan_to_num(v.mean(dim=2), nan=-float("inf")).argmax(dim=1)
+
+        (weight the mean by the bag in ``meta`` bits 52-63 to follow the sampler exactly; add the first ply's
+        own reward, ``expand()[0].lines``, for a score that counts both placements)."""
+        if self._stream is not None:
+            raise ValueError("two_ply_values: an env in replay mode (piece_stream / numpy_seeds) cannot be expanded")
+        B, A, P, dev = self.batch_size, self.a_max, len(self.piece_names), self.device
+        child = getattr(self, "_two_ply_child", None)
+        if child is None:
+            child = self._two_ply_child = self._child_batch(auto_reset=False, compute_obs=False)
+        parent, action, present = self._dense_children()
+        out = torch.empty((B, A, P), dtype=torch.float32, device=dev)
+        nan = torch.full((B, A), float("nan"), dtype=torch.float32, device=dev)
+        ninf = torch.full((B, A), -float("inf"), dtype=torch.float32, device=dev)
+        for p in range(P):
+            child.expand_from(self, parent, action, p)
+            _, value = child.greedy_actions(weights)
+            over = (child.n_valid == 0).view(B, A)
+            out[:, :, p] = torch.where(present, torch.where(over, ninf, value.view(B, A)), nan)
+        return out
 
     def fork(self, index, env_offset=None, seed=None):
         """A NEW VecTetris of ``len(index)`` envs, env j a copy of ``self[index[j]]`` (bag included), with this
