@@ -67,7 +67,8 @@ enum {
   TETRIS_E_STRIDE = -8,      /* afterstate strides not multiples of 4 floats / too small / matrix beyond 2^32 float4 */
   TETRIS_E_OVERLAP = -9,     /* tetris_hip_gather_envs / tetris_hip_expand_envs: source and destination storage overlap */
   TETRIS_E_ALIGN = -10,      /* softmax calls: weights / score / score_total not 16-byte aligned */
-  TETRIS_E_TEMPERATURE = -11 /* softmax calls: temperature (or 1 / temperature) not positive and finite */
+  TETRIS_E_TEMPERATURE = -11,/* softmax calls: temperature (or 1 / temperature) not positive and finite */
+  TETRIS_E_VALUE = -12       /* tetris_hip_policy_two_ply: death_value is NaN or +inf */
 };
 
 /* Constructor arguments of game.Tetris (game.py:21-23) that shape the kernels. */
@@ -506,6 +507,39 @@ int tetris_hip_expand_envs(const TetrisDesc* desc, const void* src_cols, const u
                            const uint8_t* next_piece, float* obs, int32_t* reward, uint8_t* done, uint8_t* lines,
                            uint8_t* n_valid, uint8_t* piece, uint32_t* status, uint64_t seed, uint64_t step_idx,
                            int64_t env_offset, int64_t B_dst, void* hip_stream);
+
+/*
+ * Two-piece lookahead in ONE launch: for every env, every placement k of its current piece and every piece p of the
+ * set, the best the greedy linear policy can reach with p on the board placement k leaves; the sum of those values
+ * over the pieces the env can draw next; and the first placement of maximal sum.  The batch form of trying every
+ * State of Tetris.get_after_states (game.py:67-80), drawing each next piece the sampler may hand out
+ * (tetromino.py:12-22: the bag) and asking get_best_policy / fitness (game.py:102-120) on it -- without the child
+ * boards ever reaching memory: one lane per (env, k) stamps placement k once, exactly as tetris_hip_step and
+ * tetris_hip_expand_envs do (land, lock, clear), and walks the placements of every p on that board in registers.
+ *  weights     : HOST pointer to 8 floats, as tetris_hip_policy_greedy (per-env weight rows are not part of this call)
+ *  death_value : what a next piece without a non-terminal placement counts in the sum; -inf or finite
+ *  values      : float32[B][a_max][n_pieces] or NULL.  values[i][k][p] = best_value of tetris_hip_policy_greedy on
+ *                the child (i, k) facing piece p -- the same float32 left-to-right evaluation, the same first maximum
+ *                -- or -inf when p has no non-terminal placement there
+ *  q           : float32[B][a_max] or NULL.  q[i][k] = sum over the pieces p of env i's bag, in ascending p, of
+ *                values[i][k][p] with -inf replaced by death_value: float32 additions starting from the first term,
+ *                never contracted, NOT divided by the count (it is the same for every k of an env, so the argmax is
+ *                the mean's and the sum is reproducible bit for bit in NumPy float32).  The bag is meta bits 52-63
+ *                within the set; an empty bag stands for the whole set, as the next draw refills it
+ *  n_bag       : uint8[B] or NULL: the number of pieces summed (q / n_bag is the mean)
+ *  best_action : int32[B] or NULL: the k < n_valid of maximal q[i][k], of several that reach it exactly the lowest
+ *                (an env whose sums are all -inf gets 0); -1 for an env without a non-terminal placement
+ *  best_value  : float32[B] or NULL: q at best_action; 0 where best_action is -1
+ * For k >= n_valid of env i (every k of an env that is over) values[i][k][.] and q[i][k] are NaN.  n_valid is the
+ * count in meta's valid mask, as tetris_hip_step reads it.  cols and meta are only read; nothing is drawn, so replay
+ * streams do not matter.  Any subset of the five outputs may be NULL: a NULL output is not touched, and with all of
+ * them NULL the call succeeds without a launch.  Nothing outside [B][a_max][n_pieces], [B][a_max] and [B] is written.
+ * Refused before anything is launched: desc, cols, meta or weights NULL: TETRIS_E_NULL; B <= 0 or beyond the bound of
+ * tetris_hip_step: TETRIS_E_BATCH; death_value NaN or +inf: TETRIS_E_VALUE.
+ */
+int tetris_hip_policy_two_ply(const TetrisDesc* desc, const void* cols, const uint64_t* meta, const float* weights,
+                              float death_value, float* values, float* q, uint8_t* n_bag, int32_t* best_action,
+                              float* best_value, int64_t B, void* hip_stream);
 
 #ifdef __cplusplus
 }

@@ -74,6 +74,7 @@ SIGNATURES = {
     "tetris_hip_gather_envs": [_dp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp],
     "tetris_hip_expand_envs": [_dp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _u64,
                                _i64, _i64, _vp],
+    "tetris_hip_policy_two_ply": [_dp, _vp, _vp, _vp, ctypes.c_float, _vp, _vp, _vp, _vp, _vp, _i64, _vp],
 }
 EXPORTS = list(SIGNATURES) + ["tetris_hip_error_string", "tetris_hip_source_hash"]
 

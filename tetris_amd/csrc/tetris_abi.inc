@@ -4,7 +4,7 @@
 //   TET_ABI(name)       the exported symbol: tetris_hip_##name / tetris_host_##name
 //   namespace backend   what differs between a GPU and a loop over envs, each returning an error code:
 //     launch(const TetrisDesc*, const XParams&, void* stream), overloaded on the parameter blocks (the CPU harness
-//     takes those of the gather, population, softmax and expand calls from tetris_entry.hpp);
+//     takes those of the gather, population, softmax, expand and two-ply calls from tetris_entry.hpp);
 //     pack_done_bits, counter_add, policy_random, numpy_bag_stream, decode, encode, stream_link (the arguments
 //     below); error_text(code) for a positive (runtime) code; kSourceHash.
 // Nothing here launches or touches a buffer: a refused call returns before the backend is reached.
@@ -536,6 +536,34 @@ int TET_ABI(expand_envs)(const TetrisDesc* desc, const void* src_cols, const uin
   p.env_offset = (uint32_t)env_offset;
   tet::fill_step_cfg(p.cfg, desc, 0, obs != nullptr);  // never resets: a child that is over keeps its board
   tet::step_keys(seed, step_idx, p.cfg);
+  tet::build_table(desc, &p.tab);
+  return backend::launch(desc, p, hip_stream);
+}
+
+// two-piece lookahead: the value of every (first action, next piece), its sum over the env's bag and the best action
+int TET_ABI(policy_two_ply)(const TetrisDesc* desc, const void* cols, const uint64_t* meta, const float* weights,
+                            float death_value, float* values, float* q, uint8_t* n_bag, int32_t* best_action,
+                            float* best_value, int64_t B, void* hip_stream) {
+  int rc = tet::check_desc(desc);
+  if (rc) return rc;
+  if (!cols || !meta || !weights) return TETRIS_E_NULL;
+  if (B <= 0 || !batch_fits_u32_offsets(B, B)) return TETRIS_E_BATCH;
+  if (!(death_value <= 3.402823466e+38f)) return TETRIS_E_VALUE;  // NaN, +inf
+  if (!values && !q && !n_bag && !best_action && !best_value) return TETRIS_OK;  // nothing asked for
+  TwoPlyParams p{};
+  p.cols = cols;
+  p.meta = meta;
+  p.values = values;
+  p.q = q;
+  p.n_bag = n_bag;
+  p.best_action = best_action;
+  p.best_value = best_value;
+  p.B = B;
+  p.R = desc->num_rows;
+  p.a_max = desc->a_max;
+  p.n_pieces = desc->n_pieces;
+  p.death_value = death_value;
+  for (int i = 0; i < 8; ++i) p.w[i] = weights[i];
   tet::build_table(desc, &p.tab);
   return backend::launch(desc, p, hip_stream);
 }

@@ -276,6 +276,73 @@ TET_HD void play_step_env(W (&col)[C], uint64_t& meta, const float (&w)[8], cons
   env_step<W, C, NCH, 12, true, SPAD>(col, meta, pick.best_row, false, tab, lut, scratch, sstride, cfg, env, -1, -1, out);
 }
 
+// ---- two-piece lookahead ---------------------------------------------------------------------------------
+// (tetris_hip_policy_two_ply)  The pieces the sum of an env runs over: its bag (meta bits 52-63) within the set; an
+// empty bag is the whole set, as bag_draw refills it.
+TET_HD uint32_t two_ply_bag(uint64_t meta, int n_pieces) {
+  const uint32_t all = (1u << n_pieces) - 1u;
+  const uint32_t bag = meta_bag(meta) & all;
+  return bag ? bag : all;
+}
+// the first actions of an env: the placements its mask holds (env_step's count), never more than a row of q has
+TET_HD int two_ply_n_valid(uint64_t meta, int a_max) {
+  const int nv = popc(meta_mask(meta));
+  return nv < a_max ? nv : a_max;
+}
+// One (env, first action k): placement k of the current piece is stamped once -- land, lock, clear: env_step, as
+// tetris_hip_step and expand_env run it, with the next piece dictated so that nothing is drawn -- and every piece p of
+// the set is then evaluated on that board: its valid mask as env_step computes the drawn piece's, greedy_pick_env on
+// it.  value[p] = the pick's best, -inf where piece p has no non-terminal placement; written to values_row[p] when
+// given.  Returns q: the float32 sum, in ascending p from the first term, of value[p] over the pieces of `bag` with
+// -inf replaced by death_value.  k is no placement of the env: NaN, in the row too.  col is consumed (it becomes the
+// child's board).  `lut` is an AfterLut; SPAD as env_step's.
+template <typename W, int C, int NCH, bool SPAD>
+TET_HD float two_ply_lane(W (&col)[C], uint64_t meta, int k, uint32_t bag, const float (&w)[8], float death_value,
+                          int n_pieces, const SetTable& tab, const uint8_t* lut, W* scratch, int sstride, int R,
+                          float* values_row) {
+  const float nan = __builtin_nanf(""), ninf = -__builtin_inff();
+  if (k >= popc(meta_mask(meta))) {
+    if (values_row)
+      for (int p = 0; p < n_pieces; ++p) values_row[p] = nan;
+    return nan;
+  }
+  StepCfg cfg;
+  cfg.R = R;
+  cfg.n_pieces = n_pieces;
+  cfg.auto_reset = 0;
+  cfg.key_step = cfg.key_policy = 0u;
+  cfg.compute_obs = 0;
+  cfg.has_direct_by = 0;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) cfg.direct_by[j] = 1.0f;
+  StepOut out;
+  env_step<W, C, NCH, 12, true, SPAD>(col, meta, k, false, tab, lut, scratch, sstride, cfg, 0u, 0, -1, out);
+  int h[C];
+  heights_of<W, C>(col, h);
+  float q = 0.f;
+  bool first = true;
+#pragma unroll 1
+  for (int p = 0; p < n_pieces; ++p) {
+    const uint64_t mask = valid_mask<W, C, (sizeof(W) == 4 && C <= 10)>(col, h, piece_entries(tab, p), tab.fullmask[p], R);
+    const GreedyPick pick = greedy_pick_env<W, C, NCH>(col, meta_pack(mask, p, 0u), tab, lut, R, w);
+    const float v = pick.best_row < 0 ? ninf : pick.best;
+    if (values_row) values_row[p] = v;
+    if ((bag >> p) & 1u) {
+      const float t = v == ninf ? death_value : v;
+      q = first ? t : TET_FADD(q, t);
+      first = false;
+    }
+  }
+  return q;
+}
+// the pick of one env over its row of sums: GreedyPick's first maximum over the n_valid entries in ascending k (all
+// -inf: action 0; no entry: action -1, value 0)
+TET_HD GreedyPick two_ply_pick(const float* q_row, int n_valid) {
+  GreedyPick pick;
+  for (int k = 0; k < n_valid; ++k) pick.offer(q_row[k], k);
+  return pick;
+}
+
 // ---- softmax linear policy: sample, log-probability and score -----------------------------------------
 // (tetris_hip_policy_softmax_rows / tetris_hip_play_softmax; utils.py:26-38 of the reference:
 // compute_action_probabilities and grad_of_log_action_probabilities.)  One pass over afterstates_env, as
@@ -642,7 +709,25 @@ struct ExpandParams {
   tet::SetTable tab;
 };
 
+struct TwoPlyParams {
+  const void* cols;
+  const uint64_t* meta;
+  float* values;             // optional [B][a_max][n_pieces]
+  float* q;                  // optional [B][a_max]
+  uint8_t* n_bag;            // optional [B]
+  int32_t* best_action;      // optional [B]
+  float* best_value;         // optional [B]
+  int64_t B;
+  int32_t R;
+  int32_t a_max;
+  int32_t n_pieces;
+  float death_value;
+  float w[8];
+  tet::SetTable tab;
+};
+
 // the blocks travel as kernel arguments (4 KiB at the most), the table inside them
+static_assert(sizeof(TwoPlyParams) <= 4096, "kernel argument block over 4 KiB");
 static_assert(sizeof(StepManyParams) <= 4096 && sizeof(RolloutParams) <= 4096 && sizeof(AfterParams) <= 4096 &&
               sizeof(GreedyParams) <= 4096 && sizeof(ResetParams) <= 4096 && sizeof(GreedyRowsParams) <= 4096 &&
               sizeof(PlayParams) <= 4096 && sizeof(SoftmaxRowsParams) <= 4096 && sizeof(PlaySoftmaxParams) <= 4096 &&
@@ -903,6 +988,36 @@ inline void expand_host(const ExpandParams& p) {
 inline int launch(const TetrisDesc* desc, const ExpandParams& p, void*) {
   return host_variant(desc, [&](auto w, auto c, auto nch, auto cr, auto pack) {
     expand_host<decltype(w), decltype(c)::value, decltype(nch)::value, decltype(cr)::value, decltype(pack)::value>(p);
+  });
+}
+
+// The CPU twin of two_ply_kernel: a loop over envs and first actions on tet::two_ply_lane, then tet::two_ply_pick over
+// the env's row of sums -- the same ascending-p additions and the same walk as the kernel's.
+template <typename W, int C, int NCH, bool PACK>
+inline void two_ply_host(const TwoPlyParams& p) {
+  float q_row[4 * tet::kMaxCols];  // a_max <= 48: the placements one valid mask holds
+  for (int64_t i = 0; i < p.B; ++i) {
+    W col0[C];
+    tet::load_board<W, C, PACK>(static_cast<const W*>(p.cols), p.B, i, col0);
+    const uint64_t m = p.meta[i];
+    const uint32_t bag = tet::two_ply_bag(m, p.n_pieces);
+    for (int k = 0; k < p.a_max; ++k) {
+      W col[C], scratch[C];
+      for (int c = 0; c < C; ++c) col[c] = col0[c];
+      float* row = p.values ? p.values + (i * p.a_max + k) * (int64_t)p.n_pieces : nullptr;
+      q_row[k] = tet::two_ply_lane<W, C, NCH, false>(col, m, k, bag, p.w, p.death_value, p.n_pieces, p.tab, kAfterLut.bytes,
+                                                     scratch, 1, p.R, row);
+      if (p.q) p.q[i * p.a_max + k] = q_row[k];
+    }
+    const tet::GreedyPick pick = tet::two_ply_pick(q_row, tet::two_ply_n_valid(m, p.a_max));
+    if (p.n_bag) p.n_bag[i] = (uint8_t)tet::popc(bag);
+    if (p.best_action) p.best_action[i] = pick.best_row;
+    if (p.best_value) p.best_value[i] = pick.best;
+  }
+}
+inline int launch(const TetrisDesc* desc, const TwoPlyParams& p, void*) {
+  return host_variant(desc, [&](auto w, auto c, auto nch, auto, auto pack) {
+    two_ply_host<decltype(w), decltype(c)::value, decltype(nch)::value, decltype(pack)::value>(p);
   });
 }
 }  // namespace backend

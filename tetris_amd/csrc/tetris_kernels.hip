@@ -889,6 +889,54 @@ __global__ __launch_bounds__(kRolloutBlock, (after_waves<W, C>(TET_STEP_GREEDY_W
   p.returns[id] = mean;
 }
 
+// Two-piece lookahead of every env in one launch (tetris_hip_policy_two_ply): rollouts_kernel's fan-out -- one lane per
+// (env, first action), its tile, its LDS block, the afterstate tables -- with whole envs per workgroup: EPB =
+// kRolloutBlock / a_max envs, lane e * a_max + k being action k of the workgroup's e-th env; the lanes behind the last
+// whole env (a_max - 1 at the most) idle.  A lane stamps its placement once and evaluates every piece of the set on the
+// child in registers (tet::two_ply_lane); the child never reaches memory.  The sums of a workgroup meet in LDS, and
+// after one barrier the first EPB lanes each pick for one env (tet::two_ply_pick).  No lane leaves early: the staging,
+// both barriers and the pick sit outside every branch.  Plain stores only, none for a lane or an env past B.
+template <typename W, int C, int NCH>
+__global__ __launch_bounds__(kRolloutBlock, (after_waves<W, C>(TET_STEP_GREEDY_WAVES))) void two_ply_kernel(const TwoPlyParams p) {
+  constexpr int kBlock = kRolloutBlock;  // shadows the file-wide tile size inside this kernel
+  __shared__ StepLds<W, C, kBlock, 12, true> lds;
+  __shared__ float q_lds[kBlock];
+  SetTable& tab = lds.tab;
+  uint8_t* const hole_lut = lds.lut;
+  auto& lane_cols = lds.lane_cols;
+  constexpr bool SPAD = tet::scratch_padded<W, C, NCH, 12, true>();
+  static_assert(sizeof(lds.lane_cols) / sizeof(lds.lane_cols[0]) >= (SPAD ? C + 3 : C), "the unclamped stamp needs its three columns");
+  const int epb = kBlock / p.a_max;
+  const int e = (int)threadIdx.x / p.a_max;
+  const int k = (int)threadIdx.x - e * p.a_max;
+  const int64_t i = (int64_t)blockIdx.x * epb + e;
+  const bool live = e < epb && i < p.B;
+  const int64_t ii = live ? i : 0;  // (an env every launch has: the loads sit in front of the staging)
+  W col[C];
+  tet::load_board<W, C, (NCH != 0 && !TET_NO_PACK)>(static_cast<const W*>(p.cols), p.B, ii, col);
+  const uint64_t meta = p.meta[ii];
+  stage_after_lut(hole_lut);
+  stage_table(tab, p.tab);
+  float q = __builtin_nanf("");
+  if (live) {
+    const int64_t at = i * p.a_max + k;
+    q = tet::two_ply_lane<W, C, NCH, SPAD>(col, meta, k, tet::two_ply_bag(meta, p.n_pieces), p.w, p.death_value, p.n_pieces, tab,
+                                           hole_lut, &lane_cols[0][threadIdx.x], kBlock, p.R,
+                                           p.values ? p.values + at * p.n_pieces : nullptr);
+    if (p.q) p.q[at] = q;
+  }
+  q_lds[threadIdx.x] = q;
+  __syncthreads();
+  const int64_t i2 = (int64_t)blockIdx.x * epb + threadIdx.x;
+  if ((int)threadIdx.x < epb && i2 < p.B) {
+    const uint64_t m2 = p.meta[i2];
+    const tet::GreedyPick pick = tet::two_ply_pick(&q_lds[threadIdx.x * p.a_max], tet::two_ply_n_valid(m2, p.a_max));
+    if (p.n_bag) p.n_bag[i2] = (uint8_t)tet::popc(tet::two_ply_bag(m2, p.n_pieces));
+    if (p.best_action) p.best_action[i2] = pick.best_row;
+    if (p.best_value) p.best_value[i2] = pick.best;
+  }
+}
+
 // dst env j := src env index[j] (tet::gather_env), one lane per dst env, for any column count: the planes are
 // opaque words, NP of them (tet::gather_variant).  The index load (coalesced) is in flight while the twelve fullmask words are staged; the body then
 // issues the gathered plane and meta loads back to back and stores the dst tile record, meta, n_valid and piece
@@ -1159,7 +1207,15 @@ struct LaunchExpand {
     });
   }
 };
-
+template <typename W, int C>
+struct LaunchTwoPly {
+  static void run(const TwoPlyParams& p, hipStream_t s) {
+    tet::kernel_variant<W>(p.R, [&](auto nch, auto, auto) {
+      const int64_t epb = kRolloutBlock / p.a_max;  // whole envs per workgroup
+      hipLaunchKernelGGL((two_ply_kernel<W, C, decltype(nch)::value>), dim3((unsigned)((p.B + epb - 1) / epb)), dim3(kRolloutBlock), 0, s, p);
+    });
+  }
+};
 
 template <> struct LaunchId<LaunchStep> { static constexpr int value = 0; };
 template <> struct LaunchId<LaunchStepMany> { static constexpr int value = 1; };
@@ -1173,6 +1229,7 @@ template <> struct LaunchId<LaunchPlay> { static constexpr int value = 8; };
 template <> struct LaunchId<LaunchSoftmaxRows> { static constexpr int value = 9; };
 template <> struct LaunchId<LaunchPlaySoftmax> { static constexpr int value = 10; };
 template <> struct LaunchId<LaunchExpand> { static constexpr int value = 11; };
+template <> struct LaunchId<LaunchTwoPly> { static constexpr int value = 12; };
 
 template <template <typename, int> class Launcher, int CC, typename P>
 inline void launch_words(int word_bytes, const void* p, hipStream_t s) {
@@ -1195,6 +1252,7 @@ int launch_part(int which, int word_bytes, const void* p, hipStream_t s) {
     case 9: launch_words<LaunchSoftmaxRows, CC, SoftmaxRowsParams>(word_bytes, p, s); break;
     case 10: launch_words<LaunchPlaySoftmax, CC, PlaySoftmaxParams>(word_bytes, p, s); break;
     case 11: launch_words<LaunchExpand, CC, ExpandParams>(word_bytes, p, s); break;
+    case 12: launch_words<LaunchTwoPly, CC, TwoPlyParams>(word_bytes, p, s); break;
     default: return TETRIS_E_DESC;
   }
   return (int)hipGetLastError();
@@ -1258,6 +1316,7 @@ int launch(const TetrisDesc* d, const PlayParams& p, void* s) { return dispatch<
 int launch(const TetrisDesc* d, const SoftmaxRowsParams& p, void* s) { return dispatch<LaunchSoftmaxRows>(d, p, (hipStream_t)s); }
 int launch(const TetrisDesc* d, const PlaySoftmaxParams& p, void* s) { return dispatch<LaunchPlaySoftmax>(d, p, (hipStream_t)s); }
 int launch(const TetrisDesc* d, const ExpandParams& p, void* s) { return dispatch<LaunchExpand>(d, p, (hipStream_t)s); }
+int launch(const TetrisDesc* d, const TwoPlyParams& p, void* s) { return dispatch<LaunchTwoPly>(d, p, (hipStream_t)s); }
 
 int launch(const TetrisDesc* d, const GatherParams& p, void* s) {  // one kernel per word size and plane count, whatever the columns
   const bool known = tet::gather_variant(p.n_planes, [&](auto np) {

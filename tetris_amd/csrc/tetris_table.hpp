@@ -162,6 +162,7 @@ inline const char* error_text(int code) {
     case TETRIS_E_OVERLAP: return "source and destination storage overlap (gather into a second cols / meta pair)";
     case TETRIS_E_ALIGN: return "weights, score and score_total must be 16-byte aligned";
     case TETRIS_E_TEMPERATURE: return "temperature and 1 / temperature must be positive and finite";
+    case TETRIS_E_VALUE: return "death_value must be -inf or finite";
     default: return nullptr;
   }
 }

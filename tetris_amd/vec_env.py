@@ -840,6 +840,52 @@ class VecTetris:
             out[:, :, p] = torch.where(present, torch.where(over, ninf, value.view(B, A)), nan)
         return out
 
+    def lookahead(self, weights=None, death_value=-float("inf"), return_q=False, return_values=False):
+        """The two-piece-lookahead policy in one kernel (``tetris_hip_policy_two_ply``): for every env, the first
+        placement whose afterstate is best ON AVERAGE over the pieces the env's bag can hand out next, each next piece
+        placed greedily on the linear fitness (``weights``: 8 floats, default the BCTS vector of game.py:111-118).
+        Returns ``(action int32 [B], value float32 [B])``: the first action of maximal mean (the lowest of several
+        that reach it exactly; -1 for an env that is over) and that mean -- the kernel's float32 sum over the bag's
+        pieces in ascending order divided by their number (value 0 where the action is -1).
+
+        The table behind it is :meth:`two_ply_values`' bit for bit, but no child env is built: the child boards stay
+        in registers, so the call needs no child batch, runs at any batch size, and -- nothing being drawn -- works in
+        replay mode too.  A next piece without a non-terminal placement counts ``death_value`` in the mean (``-inf``,
+        the default: a first placement after which some piece of the bag ends the game is never preferred to one that
+        survives every piece; a finite value trades that risk; NaN and ``+inf`` are refused).
+
+        ``return_q`` appends ``q_mean float32 [B, a_max]``, the mean of every first action (NaN for
+        ``k >= n_valid``), ``return_values`` the table ``values float32 [B, a_max, n_pieces]`` (``-inf`` where the
+        child is over with that piece, NaN for ``k >= n_valid``).  The tensors are reused by the next call.  This env
+        is unchanged; play the action with :meth:`step`."""
+        w = (ctypes.c_float * 8)(*(self.BCTS_WEIGHTS if weights is None else [float(x) for x in weights]))
+        B, A, P, dev = self.batch_size, self.a_max, len(self.piece_names), self.device
+        if not hasattr(self, "_la_action"):
+            self._la_action = torch.empty(B, dtype=torch.int32, device=dev)
+            self._la_value = torch.empty(B, dtype=torch.float32, device=dev)
+            self._la_n_bag = torch.empty(B, dtype=torch.uint8, device=dev)
+            self._la_q = self._la_values = None
+        q = v = None
+        if return_q:
+            if self._la_q is None:
+                self._la_q = torch.empty((B, A), dtype=torch.float32, device=dev)
+            q = self._la_q
+        if return_values:
+            if self._la_values is None:
+                self._la_values = torch.empty((B, A, P), dtype=torch.float32, device=dev)
+            v = self._la_values
+        rc = self._lib.policy_two_ply(ctypes.byref(self.desc), _ptr(self.cols), _ptr(self.meta), w, float(death_value),
+                                      _ptr(v), _ptr(q), _ptr(self._la_n_bag), _ptr(self._la_action), _ptr(self._la_value),
+                                      B, self._hip_stream())
+        self._lib.check(rc, "tetris_hip_policy_two_ply")
+        n = self._la_n_bag.to(torch.float32)
+        out = (self._la_action, self._la_value / n)
+        if return_q:
+            out += (q / n[:, None],)
+        if return_values:
+            out += (v,)
+        return out
+
     def fork(self, index, env_offset=None, seed=None):
         """A NEW VecTetris of ``len(index)`` envs, env j a copy of ``self[index[j]]`` (bag included), with this
         env's geometry, pieces, feature_directions, auto_reset, compute_obs and afterstate_layout; ``seed`` and
